@@ -129,3 +129,87 @@ def test_stalled_runs_are_topped_up_and_left_out_of_the_median():
     # three clean runs: nothing extra
     rs3 = [_run(600, 700), _run(610, 700), _run(620, 700)]
     assert bench.top_up(rs3, lambda: None) == 0 and bench.p50_run(rs3)["p50_us"] == 610
+
+
+def test_bench_batch_flips_one_message_bit_in_a_seeded_sixteenth(monkeypatch):
+    """The bench batch: n // 16 signatures, the same ones on every call, differ from the signed batch in exactly
+    one bit of their own message; keys, signatures and layout are untouched; the default leaves the batch whole."""
+    import numpy as np
+    import bench
+    from firedancer_amd import workload
+    n, m = 1 << 12, 200
+
+    def signed(n, m, seed):
+        rng = np.random.default_rng(seed)
+        return (rng.integers(0, 256, (n, 32), dtype=np.uint8), rng.integers(0, 256, (n, 64), dtype=np.uint8),
+                (np.arange(n) * m).astype(np.uint32), np.full(n, m, np.uint32),
+                rng.integers(0, 256, n * m + 1, dtype=np.uint8))
+    monkeypatch.setattr(workload, "sig_batch", signed)
+    whole = bench.make_workload(n, m, 1000)
+    a, b = bench.make_workload(n, m, 1000, bench.FLIP_ONE_IN), bench.make_workload(n, m, 1000, bench.FLIP_ONE_IN)
+    assert all(np.array_equal(x, y) for x, y in zip(a, b))
+    assert all(np.array_equal(x, y) for x, y in zip(whole, signed(n, m, 1000)))
+    assert all(np.array_equal(x, y) for x, y in zip(a[:4], whole[:4]))
+    d = np.nonzero(a[4] != whole[4])[0]
+    assert d.size == n // bench.FLIP_ONE_IN == np.unique(d // m).size and d.max() < n * m
+    assert all(bin(int(x)).count("1") == 1 for x in a[4][d] ^ whole[4][d])
+    other = bench.make_workload(n, m, 1001, bench.FLIP_ONE_IN)[4]
+    assert not np.array_equal(np.nonzero(other != signed(n, m, 1001)[4])[0] // m, d // m)
+
+
+def test_dump_outputs_float32_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 files named after the arrays (other ranks' with their rank), whole when they fit
+    their share of the cap, else the same sorted sample on every call."""
+    import numpy as np
+    import bench
+    err = (np.arange(1000) % 7 - 3).astype(np.int8)
+    bench.dump_outputs(str(tmp_path / "a"), {"verdicts": err})
+    got = np.load(tmp_path / "a" / "verdicts.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, err.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 2 * 2 * 100)   # 2 ranks x 2 arrays x 100 elements
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"txn_verdicts": err[:100], "sig_verdicts": err}, rank=1, world=2)
+    whole = np.load(tmp_path / "b" / "txn_verdicts_rank1.npy")
+    cut = np.load(tmp_path / "b" / "sig_verdicts_rank1.npy")
+    assert np.array_equal(whole, err[:100].astype(np.float32))
+    assert cut.dtype == np.float32 and cut.shape == (100,)
+    assert np.array_equal(cut, np.load(tmp_path / "c" / "sig_verdicts_rank1.npy"))
+    total = sum(os.path.getsize(tmp_path / "b" / f) - 128 for f in os.listdir(tmp_path / "b"))
+    assert total <= bench.DUMP_MAX_BYTES // 2
+
+
+def test_plain_run_line_and_options(monkeypatch, capsys):
+    """A plain run's line: the headline keys, no side file; --full and --dump-outputs parse, off by default."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 3
+    monkeypatch.setattr(bench, "write_detail", lambda out, args: (_ for _ in ()).throw(AssertionError("side file")))
+    out = {k: v for k, v in _out(None).items() if k != "stream_tile"}
+    bench.emit(out, args)
+    line = json.loads(capsys.readouterr().out.strip())
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line
+    assert line["detail"] is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "d"
+
+
+def test_full_run_without_the_compiled_reference_says_so(monkeypatch, tmp_path, capsys):
+    """--full where oracle/_ref was not built: no CPU baseline, named in the line; never the port in its place."""
+    import bench
+    monkeypatch.setattr(bench, "REF_BATCH_SO", str(tmp_path / "missing.so"))
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    args = bench.parse()
+    bench.cpu_baseline_or_skip(args)
+    assert args.no_cpu is True
+    monkeypatch.setattr(bench, "write_detail", lambda out, args: "d.json")
+    bench.emit({k: v for k, v in _out(None).items() if k != "stream_tile"}, args)
+    line = json.loads(capsys.readouterr().out.strip())
+    assert "cpu_baseline" not in line and "missing.so" in line["cpu_baseline_skipped"]
+    # a plain run never needs it
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    args = bench.parse()
+    bench.cpu_baseline_or_skip(args)
+    assert args.no_cpu is False and not hasattr(args, "cpu_skipped")

@@ -110,8 +110,8 @@ def test_golden_fixtures_regenerate_identically():
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not (os.path.isdir("/root/reference/src") and os.path.exists(os.path.join(root, "oracle", "_ref", "gen_golden"))):
-        pytest.skip("needs /root/reference and oracle/_ref (build container)")
+    if not os.path.exists(os.path.join(root, "oracle", "_ref", "gen_golden")):
+        pytest.skip("oracle/_ref not built (build() compiles it only where the reference's sources are)")
     r = subprocess.run([os.path.join(root, "tools", "regen_golden.sh")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.count("identical to the committed fixture") == 3

@@ -11,7 +11,7 @@ for r in 1 2; do
     FD_AMD_DSM8=$v timeout -k 10 120 python3 tools/dsm4_scaling.py 2>/dev/null | python3 -c "
 import json,sys
 print(' '.join('%d:%.3f' % (d['n'], d['k_dsm4_ms']) for d in map(json.loads, sys.stdin)))"
-    FD_AMD_DSM8=$v timeout -k 10 200 python3 bench.py --steps 2 --warmup 1 --no-stream --no-cpu 2>/dev/null | python3 -c "
+    FD_AMD_DSM8=$v timeout -k 10 200 python3 bench.py --full --steps 2 --warmup 1 --no-stream --no-cpu 2>/dev/null | python3 -c "
 import json,sys; d=json.load(sys.stdin); print('p50 staged %.4f registered %.4f dropin %.1f us' % (d['latency_ms_4096']['p50'], d['latency_ms_4096_registered']['p50'], d['dropin_call_us']['p50']))"
   done
 done

@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
   || { echo "gpu tests failed"; tail -30 $O/gpu_tests.log; exit 1; }
 tail -2 $O/gpu_tests.log
 FD_AMD_DEVICE_MAP=mod timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29521 bench.py --gpus 2 --steps 4 --warmup 1 --no-cpu > $O/bench_2rank.json 2> $O/bench_2rank.err \
+  --master-port 29521 bench.py --full --gpus 2 --steps 4 --warmup 1 --no-cpu > $O/bench_2rank.json 2> $O/bench_2rank.err \
   || { echo "2-rank bench failed"; tail -20 $O/bench_2rank.err; exit 1; }
 echo "2-rank ok"
 cut -c1-600 $O/bench_2rank.json

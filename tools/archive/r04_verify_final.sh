@@ -7,7 +7,7 @@ O=gpurun_out/r04_verify; mkdir -p $O
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $O/gpu_tests.log 2>&1 \
   || { echo "gpu tests failed"; tail -30 $O/gpu_tests.log; exit 1; }
 tail -1 $O/gpu_tests.log
-timeout -k 10 300 python3 bench.py --steps 5 --warmup 1 --no-cpu --no-stream --no-host-fed > $O/bench_latency.json 2> $O/bench_latency.err \
+timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 1 --no-cpu --no-stream --no-host-fed > $O/bench_latency.json 2> $O/bench_latency.err \
   || { echo "bench failed"; tail -20 $O/bench_latency.err; exit 1; }
 python3 -c "
 import json; d=json.loads(open('$O/bench_latency.json').read().strip().splitlines()[-1])

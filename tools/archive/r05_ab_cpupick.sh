@@ -5,7 +5,7 @@
 o=$1; rounds=${2:-2}; mkdir -p $o
 for i in $(seq 1 $rounds); do
   for V in top quiet; do
-    FD_AMD_BENCH_CPU_PICK=$V timeout -k 10 400 python bench.py --steps 3 --warmup 1 --no-cpu --no-latency --no-host-fed \
+    FD_AMD_BENCH_CPU_PICK=$V timeout -k 10 400 python bench.py --full --steps 3 --warmup 1 --no-cpu --no-latency --no-host-fed \
       --detail $o/detail_${V}_$i.json > $o/line_${V}_$i.json 2> $o/err_${V}_$i.txt || exit 1
     grep "spinning threads" $o/err_${V}_$i.txt | head -1
     python3 -c "

@@ -2,7 +2,7 @@
 # Sample the GPU's power and shader clock while the bench runs (is the
 # pipelined bench power-bound?).  usage: tools/clock_probe.sh [bench args...]
 O=gpurun_out/clock; mkdir -p $O
-timeout -k 10 200 python3 bench.py --no-cpu --no-latency --no-stream "$@" > $O/bench.json 2> $O/bench.err &
+timeout -k 10 200 python3 bench.py --full --no-cpu --no-latency --no-stream "$@" > $O/bench.json 2> $O/bench.err &
 B=$!
 for i in $(seq 60); do
   kill -0 $B 2>/dev/null || break

@@ -19,10 +19,10 @@ case "$2" in
 bench)
   timeout -k 10 300 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $O/gpu_tests.log 2>&1 || { echo "gpu tests failed"; tail -20 $O/gpu_tests.log; exit 1; }
   echo "gpu tests ok"
-  timeout -k 10 600 python3 bench.py --detail $O/bench_detail.json > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full --detail $O/bench_detail.json > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
   echo "bench ok" ;;
 prof)
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --steps 5 --warmup 1 \
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --full --steps 5 --warmup 1 \
     --streams 1 --no-cpu --no-latency --no-stream --no-host-fed > $O/prof.log 2>&1 || { echo "rocprof failed"; tail -20 $O/prof.log; exit 1; }
   echo "rocprof ok"
   bash tools/prof_pmc.sh $O/pmc > $O/pmc.log 2>&1 || { echo "pmc failed"; tail -20 $O/pmc.log; exit 1; }
@@ -31,11 +31,11 @@ prof)
   timeout -k 10 600 bash tools/prof_tile.sh $T/prof_tile 4194304 > $O/prof_tile.log 2>&1 || { echo "tile prof failed"; tail -20 $O/prof_tile.log; exit 1; }
   echo "tile prof ok" ;;
 multi)
-  timeout -k 10 300 python3 bench.py --workload txn --steps 5 --warmup 1 --detail $O/txn_detail.json > $O/txn.json 2> $O/txn.err || { echo "txn bench failed"; tail -20 $O/txn.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --workload txn --steps 5 --warmup 1 --detail $O/txn_detail.json > $O/txn.json 2> $O/txn.err || { echo "txn bench failed"; tail -20 $O/txn.err; exit 1; }
   echo "txn ok"
-  FD_AMD_DEVICE_MAP=mod timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 > $O/bench_2rank.json 2> $O/bench_2rank.err || { echo "2-rank bench failed"; tail -20 $O/bench_2rank.err; exit 1; }
+  FD_AMD_DEVICE_MAP=mod timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 > $O/bench_2rank.json 2> $O/bench_2rank.err || { echo "2-rank bench failed"; tail -20 $O/bench_2rank.err; exit 1; }
   echo "2-rank ok"
-  FD_AMD_DEVICE_MAP=mod timeout -k 10 300 python3 bench.py --multi-engine --gpus 2 --steps 4 --warmup 1 > $O/multi_engine_2.json 2> $O/multi_engine_2.err || { echo "multi-engine failed"; tail -20 $O/multi_engine_2.err; exit 1; }
+  FD_AMD_DEVICE_MAP=mod timeout -k 10 300 python3 bench.py --full --multi-engine --gpus 2 --steps 4 --warmup 1 > $O/multi_engine_2.json 2> $O/multi_engine_2.err || { echo "multi-engine failed"; tail -20 $O/multi_engine_2.err; exit 1; }
   echo "multi-engine ok" ;;
 sweep)
   if [ "$3" = "a" ]; then S="0:k_dsmp 1:k_dsmp 2:k_dsmp 3:k_dsmp"; else S="4:k_dsmp 5:k_dsmp 0:k_dsm8 1:k_dsm8"; fi

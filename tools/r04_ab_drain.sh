@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/r04_ab_drain; mkdir -p $O
 for r in 1 2 3; do
   for v in 0 1; do
-    FD_AMD_LIB=firedancer_amd/libfd_ab_drainprio$v.so timeout -k 10 200 python3 bench.py --steps 10 --warmup 2 \
+    FD_AMD_LIB=firedancer_amd/libfd_ab_drainprio$v.so timeout -k 10 200 python3 bench.py --full --steps 10 --warmup 2 \
       --no-cpu --no-latency --no-host-fed --no-stream > $O/prio${v}_$r.json 2> $O/prio${v}_$r.err \
       || { echo "bench prio$v run $r failed"; tail -20 $O/prio${v}_$r.err; exit 1; }
     python3 -c "

@@ -9,10 +9,10 @@ for i in $(seq 1 $rounds); do
     for Q in default $qs; do
       echo "== hwq $Q streams $S round $i" >> $out
       if [ "$Q" = default ]; then
-        timeout -k 10 120 python bench.py --steps 30 --warmup 5 --streams $S --no-stream --no-cpu --no-latency \
+        timeout -k 10 120 python bench.py --full --steps 30 --warmup 5 --streams $S --no-stream --no-cpu --no-latency \
           --no-host-fed --detail /tmp/d.json >> $out 2>&1 || exit 1
       else
-        GPU_MAX_HW_QUEUES=$Q timeout -k 10 120 python bench.py --steps 30 --warmup 5 --streams $S --no-stream --no-cpu \
+        GPU_MAX_HW_QUEUES=$Q timeout -k 10 120 python bench.py --full --steps 30 --warmup 5 --streams $S --no-stream --no-cpu \
           --no-latency --no-host-fed --detail /tmp/d.json >> $out 2>&1 || exit 1
       fi
     done
