@@ -8,6 +8,7 @@ Outputs:
                                           FD_AMD_DIAG measurement aids (k_tile_synth, the pool's and the
                                           tile kernel's clocks) -- tools only, never the product
     oracle/liboracle.so                   CPU restatement (checker only)
+    tests/hip/libfd_probe.so              probe kernels around the device field ops (tests only)
     oracle/_ref/libfdref.so               the reference's own sources, compiled
                                           (only when /root/reference exists)
 """
@@ -190,10 +191,31 @@ def build_clients(verbose=False):
     return exe
 
 
+PROBE_SRC = os.path.join(ROOT, "tests", "hip", "fd_probe.hip")
+PROBE_LIB = os.path.join(ROOT, "tests", "hip", "libfd_probe.so")
+
+
+def build_probe(force=False, verbose=False):
+    """tests/hip/libfd_probe.so: probe kernels around the device field and
+    group functions (test infrastructure; includes fd_ed25519_kernels.hip,
+    same hipcc flags as the engine, never linked into the product)."""
+    deps = [PROBE_SRC] + [os.path.join(CSRC, s) for s in ("fd_ed25519_kernels.hip", "fd_ed25519_consts.h") + tuple(HEADERS)]
+    if not force and not _stale(PROBE_LIB, deps):
+        return PROBE_LIB
+    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
+           "-shared", PROBE_SRC, "-o", PROBE_LIB + ".tmp"]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd, cwd=os.path.dirname(PROBE_SRC))
+    os.replace(PROBE_LIB + ".tmp", PROBE_LIB)
+    return PROBE_LIB
+
+
 def build(force=False, verbose=False):
     build_oracle(verbose)
     so = build_engine(force, verbose)
     build_clients(verbose)
+    build_probe(force, verbose)
     return so
 
 

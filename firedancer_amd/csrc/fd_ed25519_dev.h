@@ -325,7 +325,12 @@ FD_DEV fe fe_sq( fe const & f ) { return fe_sq_fold( f ); }
    taken from f19[j] (j >= 5 whenever i + j >= 10).  For |f| <= 2^26 no
    operand wraps (f << 3 <= 2^29, 19 f <= 2^30.25), so the column sums are
    the exact integers sum_{i+j=K} c_ij f_i f_j -- the sums of fe_mul( f, f )
-   (resp. fe_mul( f, f+f )) -- and the carry gives the same limbs. */
+   (resp. fe_mul( f, f+f )) -- and the carry gives the same limbs.  The
+   reference's own square (FE_AVX_INL_SQN) wraps its 38 f of limbs 5, 7, 9
+   above |f| = floor((2^31-1)/38) ~ 2^25.75, so these are the reference's
+   limbs for even |limb| <= 2^26 and odd |limb| <= 2^25.75; the callers feed
+   X+Y of carried limbs (even <= 2^26, odd <= 2^25 + 2), inside it
+   (tests/test_fe_ref_cpu.py::test_sq_term_domain_edge). */
 template<int K, bool D2>
 FD_DEV void sq_term( int i, i32 const * f, i32 const * f19, i64 & a ) {
   int const j = (K - i + 10) % 10;

@@ -758,6 +758,21 @@ fd_ed25519_amd_debug_digits_dev( ulong n, void const * d_ws, ushort * d_dig, int
   return FD_ED25519_AMD_OK;
 }
 
+extern "C" int
+fd_ed25519_amd_debug_points_dev( ulong n, void const * d_ws, int * d_A, int * d_R, uchar * d_ds, void * stream ) {
+  if( !n ) return FD_ED25519_AMD_OK;
+  if( !d_ws || !d_A || !d_R || !d_ds ) return FD_ED25519_AMD_ERR_INVAL;
+  ws_layout_t L = fd_amd_ws_layout( n );
+  uint8_t const * ws = (uint8_t const *)d_ws;
+  /* the planes are [limb][L.N]: one copy per limb packs them to [limb][n] (a debug path) */
+  for( ulong k=0; k<30UL; k++ )
+    HIPCHK( hipMemcpyAsync( d_A + k*n, ws + L.A + 4UL*k*L.N, 4UL*n, hipMemcpyDeviceToDevice, (hipStream_t)stream ) );
+  for( ulong k=0; k<20UL; k++ )
+    HIPCHK( hipMemcpyAsync( d_R + k*n, ws + L.R + 4UL*k*L.N, 4UL*n, hipMemcpyDeviceToDevice, (hipStream_t)stream ) );
+  HIPCHK( hipMemcpyAsync( d_ds, ws + L.ds, 2UL*n, hipMemcpyDeviceToDevice, (hipStream_t)stream ) );
+  return FD_ED25519_AMD_OK;
+}
+
 /* ------------------------------------------------------------------ */
 /* drop-in reference API                                                */
 

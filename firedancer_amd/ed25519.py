@@ -66,6 +66,8 @@ def lib():
     L.fd_ed25519_amd_work_stats_dev.restype = i
     L.fd_ed25519_amd_debug_digits_dev.argtypes = [ul, vp, vp, vp, vp]
     L.fd_ed25519_amd_debug_digits_dev.restype = i
+    L.fd_ed25519_amd_debug_points_dev.argtypes = [ul, vp, vp, vp, vp, vp]
+    L.fd_ed25519_amd_debug_points_dev.restype = i
     L.fd_ed25519_amd_version.argtypes = []
     L.fd_ed25519_amd_version.restype = ctypes.c_char_p
     L.fd_ed25519_amd_sign_batch.argtypes = [ul, vp, vp, vp, vp, vp, vp, i]
@@ -465,6 +467,15 @@ def debug_digits_dev(n, d_ws, d_dig, d_top, stream=0):
     rc = lib().fd_ed25519_amd_debug_digits_dev(int(n), d_ws, d_dig, d_top, stream)
     if rc:
         raise EngineError("fd_ed25519_amd_debug_digits_dev rc=%d" % rc)
+
+
+def debug_points_dev(n, d_ws, d_A, d_R, d_ds, stream=0):
+    """Copy the decompression planes of the last device-resident call: d_A
+    int32 [30][n] (-A.X, A.Y, -A.T), d_R int32 [20][n] (R.X, R.Y), d_ds uint8
+    [n][2] (status of A / R)."""
+    rc = lib().fd_ed25519_amd_debug_points_dev(int(n), d_ws, d_A, d_R, d_ds, stream)
+    if rc != 0:
+        raise EngineError("fd_ed25519_amd_debug_points_dev rc=%d" % rc)
 
 
 def sign_dev(n, d_prv, d_off, d_sz, d_blob, d_pub, d_sig, stream=0):

@@ -311,6 +311,15 @@ fd_ed25519_amd_work_stats_dev( ulong n, void const * d_ws, uint * d_stats, void 
 int
 fd_ed25519_amd_debug_digits_dev( ulong n, void const * d_ws, unsigned short * d_dig, int * d_top, void * stream );
 
+/* Debug: copy the decompression's output that the last device-resident
+   call left in workspace `d_ws`: d_A int [30][n] (-A.X, A.Y, -A.T limbs;
+   A.Z == 1), d_R int [20][n] (R.X, R.Y limbs), d_ds uchar [n][2]
+   (decompression status of A / R: 0 ok, 1 not on the curve; limbs are
+   valid only where the status is 0 and the s check passed).  Reference:
+   avx/fd_ed25519_ge.c:221-299 and the negation of user.c:406-407. */
+int
+fd_ed25519_amd_debug_points_dev( ulong n, void const * d_ws, int * d_A, int * d_R, unsigned char * d_ds, void * stream );
+
 /* Host-side batch keygen + sign over the SoA layout (workload synthesis;
    not the verify path): prv[n][32] -> pub[n][32], sig[n][64] over
    blob[msg_off[i] .. +msg_sz[i]), on nthread host threads.  Returns 0. */

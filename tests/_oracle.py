@@ -46,8 +46,108 @@ def oracle():
         L.oracle_txn_parse_fail_line.restype = ctypes.c_ulong
         L.oracle_txn_verify_batch.argtypes = [ctypes.c_ulong, vp, vp, vp, vp, vp, vp, ctypes.c_int]
         L.oracle_txn_verify_batch.restype = ctypes.c_int
+        ci = ctypes.c_int
+        for name, args in (("oracle_fe_mul", [vp, vp, vp]), ("oracle_fe_sqn", [vp, vp, ci]),
+                           ("oracle_fe_pow22523", [vp, vp]), ("oracle_fe_frombytes", [vp, vp]),
+                           ("oracle_fe_tobytes", [vp, vp]), ("oracle_ge_dbl", [vp, vp]),
+                           ("oracle_ge_add", [vp, vp, vp, ci]), ("oracle_ge_p1p1_to_p3", [vp, vp]),
+                           ("oracle_ge_to_cached", [vp, vp]), ("oracle_slide", [vp, vp]),
+                           ("oracle_opmax_enable", [ci]), ("oracle_opmax_reset", []), ("oracle_opmax_get", [vp])):
+            getattr(L, name).argtypes = args
+            getattr(L, name).restype = None
+        L.oracle_decompress2.argtypes = [vp, vp, vp, vp]
+        L.oracle_decompress2.restype = ci
         _o = L
     return _o
+
+
+# ---- limb-level exports (field elements: lists of ten ints; points: lists of elements) ----
+
+def _limbs_in(*fes):
+    return np.ascontiguousarray(np.array([v for f in fes for v in f], np.int64).astype(np.int32))
+
+
+def _call_limbs(name, n_out, *args):
+    out = np.zeros(10 * n_out, np.int32)
+    getattr(oracle(), name)(_p(out), *args)
+    o = out.tolist()
+    return [o[10 * k:10 * k + 10] for k in range(n_out)]
+
+
+def fe_mul(f, g):
+    a, b = _limbs_in(f), _limbs_in(g)
+    return _call_limbs("oracle_fe_mul", 1, _p(a), _p(b))[0]
+
+
+def fe_sqn(f, n=1):
+    a = _limbs_in(f)
+    return _call_limbs("oracle_fe_sqn", 1, _p(a), n)[0]
+
+
+def fe_pow22523(f):
+    a = _limbs_in(f)
+    return _call_limbs("oracle_fe_pow22523", 1, _p(a))[0]
+
+
+def fe_frombytes(s):
+    return _call_limbs("oracle_fe_frombytes", 1, bytes(s))[0]
+
+
+def fe_tobytes(f):
+    out = ctypes.create_string_buffer(32)
+    a = _limbs_in(f)
+    oracle().oracle_fe_tobytes(out, _p(a))
+    return out.raw
+
+
+def ge_dbl(X, Y, Z):
+    a = _limbs_in(X, Y, Z)
+    return tuple(_call_limbs("oracle_ge_dbl", 4, _p(a)))
+
+
+def ge_add(u, q, neg):
+    a, b = _limbs_in(*u), _limbs_in(*q)
+    return tuple(_call_limbs("oracle_ge_add", 4, _p(a), _p(b), int(neg)))
+
+
+def ge_p1p1_to_p3(t):
+    a = _limbs_in(*t)
+    return tuple(_call_limbs("oracle_ge_p1p1_to_p3", 4, _p(a)))
+
+
+def ge_to_cached(u):
+    a = _limbs_in(*u)
+    return tuple(_call_limbs("oracle_ge_to_cached", 4, _p(a)))
+
+
+def decompress2(pub, r):
+    """(rc, A, R): the reference's 2-point decompression, limbs out; A and R
+    are (X, Y, Z, T) as int32 arrays of shape (4, 10) (A not yet negated)."""
+    A, R = np.zeros(40, np.int32), np.zeros(40, np.int32)
+    rc = oracle().oracle_decompress2(_p(A), bytes(pub), _p(R), bytes(r))
+    return rc, A.reshape(4, 10), R.reshape(4, 10)
+
+
+def slide(a):
+    """fd_ed25519_ge_slide of the 256-bit integer a: 256 digits."""
+    out = np.zeros(256, np.int8)
+    oracle().oracle_slide(_p(out), int(a).to_bytes(32, "little"))
+    return out.tolist()
+
+
+def opmax_measure(fn):
+    """Run fn() with the oracle's operand maxima enabled; returns
+    (mul even, mul odd, sqn even, sqn odd) max |limb|."""
+    o = oracle()
+    o.oracle_opmax_reset()
+    o.oracle_opmax_enable(1)
+    try:
+        fn()
+    finally:
+        o.oracle_opmax_enable(0)
+    m = np.zeros(4, np.int64)
+    o.oracle_opmax_get(_p(m))
+    return tuple(int(v) for v in m)
 
 
 def ref():

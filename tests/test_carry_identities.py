@@ -8,28 +8,7 @@ with Python integers (int64 semantics checked) over random and extreme
 column sums.  CPU only."""
 import random
 
-M64 = 1 << 64
-
-
-def i64(x):
-    x %= M64
-    return x - M64 if x >= 1 << 63 else x
-
-
-def i32(x):
-    x %= 1 << 32
-    return x - (1 << 32) if x >= 1 << 31 else x
-
-
-def ref_carry(h):
-    h = list(h)
-    def c(k, w, nxt, mul=1):
-        cc = (h[k] + (1 << (w - 1))) >> w
-        h[nxt] += cc * mul
-        h[k] -= cc << w
-    c(0, 26, 1); c(4, 26, 5); c(1, 25, 2); c(5, 25, 6); c(2, 26, 3); c(6, 26, 7)
-    c(3, 25, 4); c(7, 25, 8); c(4, 26, 5); c(8, 26, 9); c(9, 25, 0, 19); c(0, 26, 1)
-    return [i32(v) for v in h]
+from _fe_ref import i32, i64, ref_carry   # the reference chain lives with the model of the reference's arithmetic
 
 
 def biased_carry(h):

@@ -232,6 +232,53 @@ def test_prep_digits_vs_python(golden):
         assert tp[j] == (max(nz) if nz else -1)
 
 
+def test_prep_digits_crafted_s(golden):
+    """k_prep's s digits and top position on scalars a signature never
+    carries by chance (_slide.crafted_scalars): 0, 1, 2^j, 2^252-1, L-1, runs
+    of 58..192 one-bits across bits 64, 128 and 192 -- the only inputs that
+    run slide_reg's multi-word carry -- and the densest digit patterns (51
+    events; the event plane holds 64).  All are < L, so they pass the s check
+    and reach the slide; R, pub and message are those of golden vector 0 (the
+    verdict is not under test)."""
+    import _slide
+    from firedancer_amd import ed25519, hip
+    ss = _slide.crafted_scalars()
+    n = len(ss)
+    pub = np.repeat(golden.pub[:1], n, axis=0)
+    sig = np.repeat(golden.sig[:1], n, axis=0)
+    for j, a in enumerate(ss):
+        sig[j, 32:] = np.frombuffer(a.to_bytes(32, "little"), np.uint8)
+    msg = golden.msg(0)
+    blob = np.frombuffer(msg + b"\0" * 16, np.uint8)
+    d = {k: hip.DeviceBuffer.from_array(v) for k, v in
+         dict(pub=pub, sig=sig, off=np.zeros(n, np.uint32), sz=np.full(n, len(msg), np.uint32), blob=blob).items()}
+    err = hip.DeviceBuffer(n)
+    ws = hip.DeviceBuffer(ed25519.workspace_footprint(n))
+    dig = hip.DeviceBuffer(512 * n)
+    top = hip.DeviceBuffer(4 * n)
+    stream = hip.Stream()
+    ed25519.verify_dev(n, d["pub"].ptr, d["sig"].ptr, d["off"].ptr, d["sz"].ptr, d["blob"].ptr, err.ptr, ws.ptr,
+                       stream.handle)
+    ed25519.debug_digits_dev(n, ws.ptr, dig.ptr, top.ptr, stream.handle)
+    stream.synchronize()
+    dg = dig.to_array(np.uint16, 256 * n).reshape(n, 256)
+    tp = top.to_array(np.int32, n)
+    ea = _slide.slide(_slide.h_scalar(sig[0], pub[0], msg))      # the same h for every case
+    most = 0
+    for j, a in enumerate(ss):
+        eb = _slide.slide(a)
+        ga = (dg[j] & 0xff).astype(np.uint8).view(np.int8).tolist()
+        gb = (dg[j] >> 8).astype(np.uint8).view(np.int8).tolist()
+        assert gb == eb, ("s digits", hex(a), "gpu digits encode %x" % sum(v << p for p, v in enumerate(gb)))
+        assert ga == ea, ("h digits", hex(a))
+        nz = [p for p in range(256) if ea[p] or eb[p]]
+        assert tp[j] == (max(nz) if nz else -1), hex(a)
+        ev = sum(1 for v in gb if v)
+        assert ev <= 64 and sum(1 for v in ga if v) <= 64
+        most = max(most, ev)
+    assert most == 51
+
+
 @pytest.fixture(params=["k_dsm", "k_dsmp", "k_dsm4", "k_dsm8"])
 def dsm_kernel(request):
     """Run a test once per double-scalar-mult kernel (throughput per-lane and
