@@ -12,6 +12,7 @@ Outputs:
     oracle/_ref/libfdref.so               the reference's own sources, compiled
                                           (only when /root/reference exists)
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -27,8 +28,15 @@ ARCH = os.environ.get("FD_AMD_ARCH", "gfx950")
 
 SOURCES = ["fd_ed25519_kernels.hip", "fd_txn_kernels.hip", "fd_ed25519_sign.hip", "fd_ed25519_engine.cpp", "fd_ed25519_multi.cpp", "fd_ed25519_host.cpp",
            "fd_verify_tile.cpp", "fd_numa.cpp"]
-HEADERS = ["fd_ed25519_dev.h", "fd_ed25519_kernels.h", "../../include/fd_ed25519_amd.h", "../../include/fd_txn_amd.h", "../../include/fd_tango_amd.h", "fd_ed25519_engine.h",
-           "../../tools/gen_consts.py"]
+CONSTS = os.path.join(CSRC, "fd_ed25519_consts.h")
+GEN_CONSTS = os.path.join(ROOT, "tools", "gen_consts.py")
+
+
+def _header_deps():
+    """What every library is stale against besides its own sources: every
+    header under csrc/ and include/ (the generated constants among them, once
+    made) and the constants' generator."""
+    return sorted(set(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(ROOT, "include", "*.h")) + [CONSTS])) + [GEN_CONSTS]
 
 
 def _hipcc():
@@ -48,13 +56,10 @@ def _stale(out, deps):
 def build_engine(force=False, verbose=False, out=None, defines=(), vgpr_guard=True):
     """Compile every source to an object in parallel (one hipcc per file),
     then link the shared library."""
-    consts = os.path.join(CSRC, "fd_ed25519_consts.h")
-    gen = os.path.join(ROOT, "tools", "gen_consts.py")
-    if force or _stale(consts, [gen]):
-        subprocess.check_call([sys.executable, gen, consts, "FD_AMD"])
+    if force or _stale(CONSTS, [GEN_CONSTS]):
+        subprocess.check_call([sys.executable, GEN_CONSTS, CONSTS, "FD_AMD"])
     lib = out or LIB
-    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [consts]
-    if not force and not defines and not _stale(lib, deps):
+    if not force and not defines and not _stale(lib, [os.path.join(CSRC, s) for s in SOURCES] + _header_deps()):
         return lib
     objdir = os.path.join(PKG, "_obj", os.path.basename(lib).replace(".so", ""))
     os.makedirs(objdir, exist_ok=True)
@@ -133,17 +138,14 @@ def kernel_vgprs(obj, kernel):
     """VGPR count of `kernel` in a compiled .hip object (its gfx950 code
     object's metadata), or None when the LLVM tools are missing."""
     import re
-    llvm = "/opt/rocm/lib/llvm/bin"
-    if not os.path.exists(os.path.join(llvm, "llvm-readelf")):
+    d = _device_object(obj)
+    if d is None:
         return None
-    subprocess.check_call([os.path.join(llvm, "llvm-objdump"), "--offloading", obj], stdout=subprocess.DEVNULL,
-                          stderr=subprocess.DEVNULL)
-    co = obj + ".0.hipv4-amdgcn-amd-amdhsa--" + ARCH
-    host = obj + ".0.host-x86_64-unknown-linux-gnu-"
+    co, tmp = d
     try:
-        notes = subprocess.check_output([os.path.join(llvm, "llvm-readelf"), "--notes", co], text=True)
+        notes = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", co], text=True)
     finally:
-        for f in (co, host):
+        for f in tmp:
             if os.path.exists(f):
                 os.remove(f)
     i = notes.find(".name:           " + kernel)
@@ -164,7 +166,7 @@ TILE_KERNEL = "_Z14k_tile_persist18fd_amd_tile_args_t"
 
 def build_diag(force=False, verbose=False):
     """The diagnostics library (FD_AMD_DIAG): tools load it through FD_AMD_LIB."""
-    if not force and not _stale(LIB_DIAG, [os.path.join(CSRC, s) for s in SOURCES + HEADERS]):
+    if not force and not _stale(LIB_DIAG, [os.path.join(CSRC, s) for s in SOURCES] + _header_deps()):
         return LIB_DIAG
     return build_engine(force=True, verbose=verbose, out=LIB_DIAG, defines=("FD_AMD_DIAG",))
 
@@ -197,10 +199,10 @@ PROBE_LIB = os.path.join(ROOT, "tests", "hip", "libfd_probe.so")
 
 def build_probe(force=False, verbose=False):
     """tests/hip/libfd_probe.so: probe kernels around the device field and
-    group functions (test infrastructure; includes fd_ed25519_kernels.hip,
-    same hipcc flags as the engine, never linked into the product)."""
-    deps = [PROBE_SRC] + [os.path.join(CSRC, s) for s in ("fd_ed25519_kernels.hip", "fd_ed25519_consts.h") + tuple(HEADERS)]
-    if not force and not _stale(PROBE_LIB, deps):
+    group functions (test infrastructure; includes the engine's stage headers
+    up to fd_ed25519_dsm8.h, same hipcc flags as the engine, never linked into
+    the product)."""
+    if not force and not _stale(PROBE_LIB, [PROBE_SRC] + _header_deps()):
         return PROBE_LIB
     cmd = [_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
            "-shared", PROBE_SRC, "-o", PROBE_LIB + ".tmp"]

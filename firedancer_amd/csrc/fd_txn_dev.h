@@ -1,6 +1,6 @@
 /* firedancer_amd/csrc/fd_txn_dev.h -- device-side fd_txn_parse, shared by
    the transaction front end (fd_txn_kernels.hip: k_txn_parse) and the
-   streaming tile's persistent kernel (fd_ed25519_kernels.hip:
+   streaming tile's persistent kernel (fd_ed25519_tile.h:
    k_tile_persist, TXN framing).  One lane parses one untrusted wire
    transaction with the exact accept/reject behaviour and descriptor bytes of
    the reference's fd_txn_parse (src/ballet/txn/fd_txn_parse.c:6-217;

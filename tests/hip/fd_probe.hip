@@ -5,8 +5,11 @@
  * compare every variant limb for limb with the Python model of the
  * reference's arithmetic (tests/_fe_ref.py) on directed inputs.
  *
- * The product's kernel source is included verbatim (it is self-contained);
- * nothing here is linked into the product library.  Every probe is
+ * Only the product's stage headers that hold the probed functions are
+ * included, verbatim: the field ops (fd_ed25519_dev.h) and the group ops,
+ * quad and half helpers (fd_ed25519_dsm8.h, which brings in dsm4 and dsm).
+ * The front, the pool, the tile kernel and the launch code are not compiled
+ * here; nothing here is linked into the product library.  Every probe is
  * straight-line code (fixed trip counts only) on whole 64-lane waves: the
  * case count is padded with all-zero cases so every lane is active (the DPP
  * forms read neighbour lanes).
@@ -19,7 +22,8 @@
  *                half_ctx built as dsm8_body builds it
  */
 
-#include "../../firedancer_amd/csrc/fd_ed25519_kernels.hip"
+#include "../../firedancer_amd/csrc/fd_ed25519_dev.h"
+#include "../../firedancer_amd/csrc/fd_ed25519_dsm8.h"
 
 enum {
   P_MUL = 0, P_MUL_FOLD1, P_MUL_ONE, P_SQN1, P_SQN2, P_SQ_FOLD,
