@@ -381,6 +381,19 @@ dsm_lane_body( u32 i, u32 n, i8 * __restrict__ err, u8 * __restrict__ ws, ws_lay
   }
 }
 
+/* The R' = (X, Y, Z) that dsm_lane_body parked in a signature's Ai slab
+   (ints 0 / 10 / 20, the int4 stores at its PH_FIN step), for a kernel that
+   runs after k_dsm (k_strict).  Only slabs of signatures that were active
+   in the loop hold one. */
+__device__ __forceinline__ void
+dsm_load_parked( fe & X, fe & Y, fe & Z, i32 const * __restrict__ Ail ) {
+  int4 const * s_ = (int4 const *)Ail;
+  int4 w0 = s_[0], w1 = s_[1], w2 = s_[2], w3 = s_[3], w4 = s_[4], w5 = s_[5], w6 = s_[6], w7 = s_[7];
+  X = fe{{ w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y }};
+  Y = fe{{ w2.z, w2.w, w3.x, w3.y, w3.z, w3.w, w4.x, w4.y, w4.z, w4.w }};
+  Z = fe{{ w5.x, w5.y, w5.z, w5.w, w6.x, w6.y, w6.z, w6.w, w7.x, w7.y }};
+}
+
 __global__ void __launch_bounds__(64)
 k_dsm( u32 n, i8 * __restrict__ err, u8 * __restrict__ ws, ws_layout_t L, int want_stats ) {
   __shared__ __attribute__((aligned(16))) i32 bi[8][48];

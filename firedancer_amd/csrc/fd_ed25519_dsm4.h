@@ -323,6 +323,23 @@ dsm4_body( u32 gt, u32 n, i8 * __restrict__ err, u8 * __restrict__ ws, ws_layout
   }
 }
 
+/* One 12-int row of an Ai slab (10 limbs used). */
+__device__ __forceinline__ fe
+ai_row_load( i32 const * __restrict__ row ) {
+  int4 const * s_ = (int4 const *)row;
+  int4 x0 = s_[0], x1 = s_[1], x2 = s_[2];
+  return fe{{ x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w, x2.x, x2.y }};
+}
+
+/* The R' that dsm4_body parked in a signature's Ai slab, for a kernel that
+   runs after k_dsm4 (k_strict): lane q of the quad stored its own p1p1->p3
+   product in row q of entry 0, so row 0 = Z, row 1 = Y, row 2 = X (row 3 =
+   T).  Only slabs of signatures that were active in the loop hold one. */
+__device__ __forceinline__ void
+dsm4_load_parked( fe & X, fe & Y, fe & Z, i32 const * __restrict__ Ail ) {
+  Z = ai_row_load( Ail ); Y = ai_row_load( Ail + 12 ); X = ai_row_load( Ail + 24 );
+}
+
 __global__ void __launch_bounds__(64)
 k_dsm4( u32 n, i8 * __restrict__ err, u8 * __restrict__ ws, ws_layout_t L, int want_stats, i8 * __restrict__ out ) {
   __shared__ __attribute__((aligned(16))) i32 bi12[8][48];   /* the base-point table in the Ai slab's row layout */

@@ -292,6 +292,16 @@ dsm8_body( u32 gt, u32 n, i8 * __restrict__ err, u8 * __restrict__ ws, ws_layout
   }
 }
 
+/* The R' that dsm8_body parked, for a kernel that runs after k_dsm8
+   (k_strict).  Both halves (hh = 0, 1) of a signature's 8 lanes join their
+   split limbs into the same full product (fe_join5) and store it to the
+   same row Ail + qd*12, the same bytes twice: the slab ends up in k_dsm4's
+   layout, row 0 = Z, row 1 = Y, row 2 = X. */
+__device__ __forceinline__ void
+dsm8_load_parked( fe & X, fe & Y, fe & Z, i32 const * __restrict__ Ail ) {
+  dsm4_load_parked( X, Y, Z, Ail );
+}
+
 __global__ void __launch_bounds__(64)
 k_dsm8( u32 n, i8 * __restrict__ err, u8 * __restrict__ ws, ws_layout_t L, int want_stats, i8 * __restrict__ out ) {
   __shared__ __attribute__((aligned(16))) i32 bi12[8][48];

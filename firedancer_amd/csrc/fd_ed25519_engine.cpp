@@ -225,7 +225,7 @@ fd_amd_slot_launch_packed( slot_t * s, ulong n, ulong blob_sz, schar * out ) {
   bool const lat = fd_amd_uses_latency_path( (uint32_t)n, 0 ) != 0;
   if( fd_amd_launch_verify( (uint32_t)n, d, d + 32UL*n, (uint32_t *)(d + 96UL*n), (uint32_t *)(d + 100UL*n),
                             d + 104UL*n, s->d_err, s->d_ws, s->stream, 1, NULL, NULL, 0,
-                            lat ? (int8_t *)s->m_err : NULL ) )   /* latency path: verdicts written in place */
+                            lat ? (int8_t *)s->m_err : NULL, s->strict ) )   /* latency path: verdicts written in place */
     return FD_ED25519_AMD_ERR_DEVICE;
   if( !lat ) HIPCHK( slot_out( s, s->h_err, s->d_err, n ) );
   HIPCHK( hipEventRecord( s->done, s->stream ) );
@@ -262,8 +262,9 @@ fd_amd_slot_launch_txn( slot_t * s, ulong c, ulong nslot, ulong blob_sz, schar *
                                s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_skip, s->stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
   if( nslot && fd_amd_launch_verify( (uint32_t)nslot, s->d_pub, s->d_sig, s->d_off, s->d_sz, pl, s->d_err,
-                                     s->d_ws, s->stream, 0, NULL, s->d_skip, s->dsm_mode ) )
+                                     s->d_ws, s->stream, 0, NULL, s->d_skip, s->dsm_mode, NULL, s->strict ) )
     return FD_ED25519_AMD_ERR_DEVICE;
+  /* after k_strict (same stream): a transaction's verdict is its first failing signature's code in the engine's mode */
   if( fd_amd_launch_txn_reduce( (uint32_t)c, s->d_fp, s->d_tbase, s->d_err, s->d_terr, s->stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
   HIPCHK( slot_out( s, s->h_terr, s->d_terr, c ) );
@@ -487,7 +488,7 @@ slot_launch_dma( slot_t * s, ulong c, uchar const * pub, uchar const * sig, uint
   if( win ) HIPCHK( hipMemcpyAsync( s->d_blob, win_src, win, hipMemcpyHostToDevice, s->stream ) );
   if( fd_amd_launch_rebase_off( (uint32_t)c, s->d_off, s->d_sz, lo, s->stream ) ) return FD_ED25519_AMD_ERR_DEVICE;
   if( fd_amd_launch_verify( (uint32_t)c, s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_blob, s->d_err, s->d_ws, s->stream,
-                            1, NULL ) )
+                            1, NULL, NULL, 0, NULL, s->strict ) )
     return FD_ED25519_AMD_ERR_DEVICE;
   HIPCHK( slot_out( s, s->h_err, s->d_err, c ) );
   HIPCHK( hipEventRecord( s->done, s->stream ) );
@@ -518,10 +519,10 @@ fd_ed25519_amd_verify_soa_registered( fd_ed25519_amd_t * e, ulong n, uchar const
        registered planes in place over PCIe, with no copy on either side */
     slot_t * s = &e->slot[0];
     if( (rc = fd_amd_slot_drain( s )) ) return engine_quiesce( e, rc );
-    /* the DSM kernel writes the verdicts into the mapped h_err itself */
+    /* the DSM kernel (strict mode: k_strict) writes the verdicts into the mapped h_err itself */
     if( fd_amd_launch_verify( (uint32_t)n, (uint8_t const *)d[0], (uint8_t const *)d[1], (uint32_t const *)d[2],
                               (uint32_t const *)d[3], (uint8_t const *)d[4], s->d_err, s->d_ws, s->stream, 1, NULL,
-                              NULL, 0, (int8_t *)s->m_err ) )
+                              NULL, 0, (int8_t *)s->m_err, s->strict ) )
       return engine_quiesce( e, FD_ED25519_AMD_ERR_DEVICE );
     if( hipEventRecord( s->done, s->stream ) != hipSuccess ) return engine_quiesce( e, FD_ED25519_AMD_ERR_DEVICE );
     s->out = err; s->n = n; s->busy = 1; s->want_tag = 0;
@@ -664,6 +665,15 @@ extern "C" int
 fd_ed25519_amd_verify_txns_dev( ulong txn_cnt, ulong slot_cnt, uchar const * d_payload, uint const * d_txn_off,
                                 uint const * d_txn_sz, uint const * d_tbase, schar * d_txn_err, schar * d_sig_err,
                                 void * d_ws, void * stream ) {
+  return fd_ed25519_amd_verify_txns_dev_mode( txn_cnt, slot_cnt, d_payload, d_txn_off, d_txn_sz, d_tbase, d_txn_err,
+                                              d_sig_err, d_ws, stream, FD_ED25519_AMD_MODE_REFERENCE );
+}
+
+extern "C" int
+fd_ed25519_amd_verify_txns_dev_mode( ulong txn_cnt, ulong slot_cnt, uchar const * d_payload, uint const * d_txn_off,
+                                     uint const * d_txn_sz, uint const * d_tbase, schar * d_txn_err, schar * d_sig_err,
+                                     void * d_ws, void * stream, int mode ) {
+  if( mode != FD_ED25519_AMD_MODE_REFERENCE && mode != FD_ED25519_AMD_MODE_STRICT ) return FD_ED25519_AMD_ERR_INVAL;
   if( txn_cnt > 0xFFFFFFFFUL || slot_cnt > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
   if( !txn_cnt ) return FD_ED25519_AMD_OK;
   if( !d_payload || !d_txn_off || !d_txn_sz || !d_tbase || !d_txn_err || !d_ws ) return FD_ED25519_AMD_ERR_INVAL;
@@ -677,8 +687,9 @@ fd_ed25519_amd_verify_txns_dev( ulong txn_cnt, ulong slot_cnt, uchar const * d_p
     return FD_ED25519_AMD_ERR_DEVICE;
   if( slot_cnt && fd_amd_launch_verify( (uint32_t)slot_cnt, w + L.pub, w + L.sig, (uint32_t *)(w + L.off),
                                         (uint32_t *)(w + L.sz), d_payload, err, w + L.vws, st, 1, NULL,
-                                        (int8_t *)(w + L.skip) ) )
+                                        (int8_t *)(w + L.skip), 0, NULL, mode == FD_ED25519_AMD_MODE_STRICT ) )
     return FD_ED25519_AMD_ERR_DEVICE;
+  /* k_txn_reduce after k_strict, on the same stream */
   if( fd_amd_launch_txn_reduce( (uint32_t)txn_cnt, (uint32_t *)(w + L.fp), d_tbase, err, (int8_t *)d_txn_err, st ) )
     return FD_ED25519_AMD_ERR_DEVICE;
   return FD_ED25519_AMD_OK;
@@ -713,29 +724,61 @@ fd_ed25519_amd_workspace_footprint( ulong n ) {
   return fd_amd_ws_layout( n ).total;
 }
 
+static inline bool
+mode_ok( int mode ) {
+  return mode == FD_ED25519_AMD_MODE_REFERENCE || mode == FD_ED25519_AMD_MODE_STRICT;
+}
+
 extern "C" int
-fd_ed25519_amd_verify_dev( ulong n, uchar const * d_pub, uchar const * d_sig, uint const * d_msg_off,
-                           uint const * d_msg_sz, uchar const * d_blob, schar * d_err, void * d_ws, void * stream ) {
+fd_ed25519_amd_verify_dev_ev_mode( ulong n, uchar const * d_pub, uchar const * d_sig, uint const * d_msg_off,
+                                   uint const * d_msg_sz, uchar const * d_blob, schar * d_err, void * d_ws,
+                                   void * stream, void * const * ev, int mode ) {
+  if( !mode_ok( mode ) ) return FD_ED25519_AMD_ERR_INVAL;   /* before anything touches a device */
   if( n > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
   if( !n ) return FD_ED25519_AMD_OK;
   if( !d_pub || !d_sig || !d_msg_off || !d_msg_sz || !d_blob || !d_err || !d_ws ) return FD_ED25519_AMD_ERR_INVAL;
   if( fd_amd_launch_verify( (uint32_t)n, d_pub, d_sig, d_msg_off, d_msg_sz, d_blob, (int8_t *)d_err, d_ws,
-                            (hipStream_t)stream, 1, NULL ) )
+                            (hipStream_t)stream, 1, (hipEvent_t const *)ev, NULL, 0, NULL,
+                            mode == FD_ED25519_AMD_MODE_STRICT ) )
     return FD_ED25519_AMD_ERR_DEVICE;
   return FD_ED25519_AMD_OK;
+}
+
+extern "C" int
+fd_ed25519_amd_verify_dev_mode( ulong n, uchar const * d_pub, uchar const * d_sig, uint const * d_msg_off,
+                                uint const * d_msg_sz, uchar const * d_blob, schar * d_err, void * d_ws, void * stream,
+                                int mode ) {
+  return fd_ed25519_amd_verify_dev_ev_mode( n, d_pub, d_sig, d_msg_off, d_msg_sz, d_blob, d_err, d_ws, stream, NULL, mode );
+}
+
+extern "C" int
+fd_ed25519_amd_verify_dev( ulong n, uchar const * d_pub, uchar const * d_sig, uint const * d_msg_off,
+                           uint const * d_msg_sz, uchar const * d_blob, schar * d_err, void * d_ws, void * stream ) {
+  return fd_ed25519_amd_verify_dev_ev_mode( n, d_pub, d_sig, d_msg_off, d_msg_sz, d_blob, d_err, d_ws, stream, NULL,
+                                            FD_ED25519_AMD_MODE_REFERENCE );
 }
 
 extern "C" int
 fd_ed25519_amd_verify_dev_ev( ulong n, uchar const * d_pub, uchar const * d_sig, uint const * d_msg_off,
                               uint const * d_msg_sz, uchar const * d_blob, schar * d_err, void * d_ws, void * stream,
                               void * const * ev ) {
-  if( n > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
-  if( !n ) return FD_ED25519_AMD_OK;
-  if( !d_pub || !d_sig || !d_msg_off || !d_msg_sz || !d_blob || !d_err || !d_ws ) return FD_ED25519_AMD_ERR_INVAL;
-  if( fd_amd_launch_verify( (uint32_t)n, d_pub, d_sig, d_msg_off, d_msg_sz, d_blob, (int8_t *)d_err, d_ws,
-                            (hipStream_t)stream, 1, (hipEvent_t const *)ev ) )
-    return FD_ED25519_AMD_ERR_DEVICE;
+  return fd_ed25519_amd_verify_dev_ev_mode( n, d_pub, d_sig, d_msg_off, d_msg_sz, d_blob, d_err, d_ws, stream, ev,
+                                            FD_ED25519_AMD_MODE_REFERENCE );
+}
+
+/* The engine's mode: every later call of this engine launches with it.
+   Calls are synchronous (each drains its chunks), so none is in flight. */
+extern "C" int
+fd_ed25519_amd_set_mode( fd_ed25519_amd_t * e, int mode ) {
+  if( !e || !mode_ok( mode ) ) return FD_ED25519_AMD_ERR_INVAL;
+  e->mode = mode;
+  for( int k=0; k<FD_AMD_SLOT_MAX; k++ ) e->slot[k].strict = mode == FD_ED25519_AMD_MODE_STRICT;
   return FD_ED25519_AMD_OK;
+}
+
+extern "C" int
+fd_ed25519_amd_mode( fd_ed25519_amd_t const * e ) {
+  return e ? e->mode : FD_ED25519_AMD_ERR_INVAL;
 }
 
 extern "C" int

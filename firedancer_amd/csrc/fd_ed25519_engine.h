@@ -23,6 +23,7 @@ struct slot_t {
   uint64_t * h_tag;      /* dedup tags (pinned, allocated with the txn buffers) */
   int        want_tag;
   int        dsm_mode;   /* kernel path for the next launch (fd_amd_launch_verify dsm_mode) */
+  int        strict;     /* the owning engine's mode (fd_ed25519_amd_set_mode): 1 = its launches add k_strict; the tile's slots stay 0 */
   /* the chunk in flight: where its verdicts go */
   schar *    out;
   ulong      n;
@@ -47,6 +48,7 @@ struct fd_ed25519_amd {
   ulong  cap;        /* signatures per chunk */
   ulong  blob_cap;   /* message bytes per chunk */
   int    nslot;      /* 2 for the batch API (double buffering); the tile uses more */
+  int    mode;       /* FD_ED25519_AMD_MODE_*: mirrored into every slot's `strict` */
   slot_t slot[FD_AMD_SLOT_MAX];
 };
 

@@ -27,6 +27,7 @@
  *   fd_ed25519_dsm8.h   k_dsm8 (8 lanes)
  *   fd_ed25519_pool.h   k_ai, k_dsmp, k_fin (large batches)
  *   fd_ed25519_tile.h   k_tile_persist, k_tile_synth
+ *   fd_ed25519_strict.h k_strict (strict mode's overlay, after the DSM stage)
  * This file keeps the launch code and the batch-size policy.
  */
 
@@ -42,6 +43,7 @@
 #include "fd_ed25519_dsm8.h"
 #include "fd_ed25519_pool.h"
 #include "fd_ed25519_tile.h"
+#include "fd_ed25519_strict.h"
 
 /* ------------------------------------------------------------------ */
 /* launch                                                               */
@@ -169,19 +171,23 @@ fd_amd_uses_latency_path( uint32_t n, int dsm_mode ) {
 int
 fd_amd_launch_verify( u32 n, u8 const * d_pub, u8 const * d_sig, u32 const * d_off, u32 const * d_sz,
                       u8 const * d_blob, i8 * d_err, void * d_ws, hipStream_t stream, int want_stats,
-                      hipEvent_t const * ev, i8 const * d_skip, int dsm_mode, i8 * d_out ) {
+                      hipEvent_t const * ev, i8 const * d_skip, int dsm_mode, i8 * d_out, int strict ) {
   if( !n ) return 0;
   ws_layout_t L = fd_amd_ws_layout( n );
   u8 * ws = (u8 *)d_ws;
   u32 nb = (n + 63u) / 64u;
   bool small = fd_amd_uses_latency_path( n, dsm_mode );
   bool eight = dsm_mode == 3 || (dsm_mode == 0 && n <= g_dsm8_max);
+  /* strict mode: k_strict writes the verdicts that go to d_out, the DSM kernel none */
+  i8 * const dsm_out = strict ? NULL : d_out;
+  int kind;
   if( ev ) (void)hipEventRecord( ev[0], stream );
   if( small ) {   /* latency path: one front launch (hash || decompress), then k_dsm8 or k_dsm4 */
     hipLaunchKernelGGL( k_front, dim3(3u*nb), dim3(64), 0, stream, n, nb, d_pub, d_sig, d_off, d_sz, d_blob, d_err, ws, L, d_skip );
     if( ev ) { (void)hipEventRecord( ev[1], stream ); (void)hipEventRecord( ev[2], stream ); }
-    if( eight ) hipLaunchKernelGGL( k_dsm8, dim3((n + 7u)/8u), dim3(64), 0, stream, n, d_err, ws, L, want_stats, d_out );
-    else        hipLaunchKernelGGL( k_dsm4, dim3((n + 15u)/16u), dim3(64), 0, stream, n, d_err, ws, L, want_stats, d_out );
+    if( eight ) hipLaunchKernelGGL( k_dsm8, dim3((n + 7u)/8u), dim3(64), 0, stream, n, d_err, ws, L, want_stats, dsm_out );
+    else        hipLaunchKernelGGL( k_dsm4, dim3((n + 15u)/16u), dim3(64), 0, stream, n, d_err, ws, L, want_stats, dsm_out );
+    kind = eight ? STRICT_DSM8 : STRICT_DSM4;
   } else {
     bool pooled = dsm_mode == 4 || (dsm_mode == 0 && n >= g_pool_min);
     hipLaunchKernelGGL( k_prep,   dim3(nb),    dim3(64), 0, stream, n, d_pub, d_sig, d_off, d_sz, d_blob, d_err, ws, L, d_skip );
@@ -195,7 +201,11 @@ fd_amd_launch_verify( u32 n, u8 const * d_pub, u8 const * d_sig, u32 const * d_o
     } else {
       hipLaunchKernelGGL( k_dsm,  dim3(nb),    dim3(64), 0, stream, n, d_err, ws, L, want_stats );
     }
+    kind = pooled ? STRICT_DSMP : STRICT_DSM;
   }
+  if( strict )   /* the overlay: re-decide every verdict (fd_ed25519_strict.h); d_out as the DSM kernel would have used it */
+    hipLaunchKernelGGL( k_strict, dim3(nb), dim3(64), 0, stream, n, d_pub, d_sig, d_err, (u8 const *)ws, L, d_skip, kind,
+                        small ? d_out : (i8 *)NULL );
   if( ev ) (void)hipEventRecord( ev[3], stream );
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

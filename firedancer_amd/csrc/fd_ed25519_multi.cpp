@@ -124,8 +124,19 @@ fd_ed25519_amd_multi_ndev( fd_ed25519_amd_multi_t const * m ) {
   return m ? m->ndev : 0UL;
 }
 
+/* The mode of every engine.  Called between batches (one call at a time
+   per multi engine), so the workers are idle; they next read their engine
+   under run_all's lock. */
 extern "C" int
-fd_ed25519_amd_multi_verify_soa( fd_ed25519_amd_multi_t * m, ulong n, uchar const * pub, uchar const * sig,
+fd_ed25519_amd_multi_set_mode( fd_ed25519_amd_multi_t * m, int mode ) {
+  if( !m || (mode != FD_ED25519_AMD_MODE_REFERENCE && mode != FD_ED25519_AMD_MODE_STRICT) ) return FD_ED25519_AMD_ERR_INVAL;
+  std::lock_guard<std::mutex> lk( m->mu );
+  for( auto * e : m->eng ) if( fd_ed25519_amd_set_mode( e, mode ) ) return FD_ED25519_AMD_ERR_INVAL;
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" int
+fd_ed25519_amd_multi_verify_soa(fd_ed25519_amd_multi_t * m, ulong n, uchar const * pub, uchar const * sig,
                                  uint const * msg_off, uint const * msg_sz, uchar const * blob, ulong blob_sz,
                                  schar * err ) {
   if( !m || (n && (!pub || !sig || !msg_off || !msg_sz || !err)) ) return FD_ED25519_AMD_ERR_INVAL;

@@ -543,4 +543,20 @@ k_fin( u32 n, i8 * __restrict__ err, u8 * __restrict__ ws, ws_layout_t L, int wa
   }
 }
 
+/* The R' = (X, Y, Z) of a signature after k_dsmp, for a kernel that runs
+   after k_fin (k_strict): the final p1p1 that pool_store_t parked in the
+   signature's Ai slab, turned into X, Y, Z with k_fin's three products; a
+   signature with no digit at all (top < 0: h = s = 0) never entered the
+   pool and parked nothing, its R' is the identity, as in k_fin.  Only for
+   signatures that were pending when k_ai ran, and never after the step
+   guard tripped (the slabs are then unfinished). */
+__device__ __forceinline__ void
+pool_load_parked( fe & X, fe & Y, fe & Z, i32 const * __restrict__ Ail, int top ) {
+  p1p1 t;
+  if( top < 0 ) { t.X = fe_zero(); t.Y = fe_one(); t.Z = fe_one(); t.T = fe_one(); }
+  else pool_load_t( t, (int4 const *)Ail );
+  fe_mul_fold2w( Z, t.Z, t.T, Y, t.Z, t.Y );
+  X = fe_mul_fold1( t.X, t.T );
+}
+
 #endif /* FD_ED25519_POOL_H */

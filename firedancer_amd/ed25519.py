@@ -140,8 +140,13 @@ def lib():
     L.fd_verify_amd_bench_stream.argtypes = [i, ul, ul, ctypes.c_double, i, ul, ul, vp, vp, vp, vp, vp, vp, vp, ul,
                                              ul, vp]
     L.fd_verify_amd_bench_stream.restype = i
-    # entry points added in round 6 (an A/B build of an earlier round, FD_AMD_LIB, lacks them)
-    opt = {"fd_ed25519_amd_dropin_set_device": ([i], i), "fd_ed25519_amd_dropin_device": ([], i),
+    # entry points added in round 6 and later (an A/B build of an earlier round, FD_AMD_LIB, lacks them)
+    opt = {"fd_ed25519_amd_set_mode": ([vp, i], i), "fd_ed25519_amd_mode": ([vp], i),
+           "fd_ed25519_amd_multi_set_mode": ([vp, i], i),
+           "fd_ed25519_amd_verify_dev_mode": ([ul] + [vp] * 8 + [i], i),
+           "fd_ed25519_amd_verify_dev_ev_mode": ([ul] + [vp] * 9 + [i], i),
+           "fd_ed25519_amd_verify_txns_dev_mode": ([ul, ul] + [vp] * 8 + [i], i),
+           "fd_ed25519_amd_dropin_set_device": ([i], i), "fd_ed25519_amd_dropin_device": ([], i),
            "fd_ed25519_amd_dropin_pick": ([ctypes.POINTER(i), i, i, ul], i),
            "fd_verify_amd_tile_level": ([i, i] + [ctypes.c_double] * 5, i),
            "fd_verify_amd_tile_level_step": ([i, i, ul, ul, ctypes.POINTER(ul)], i)}
@@ -238,16 +243,41 @@ class EngineError(RuntimeError):
     pass
 
 
-class Engine:
-    """fd_ed25519_amd_t: one engine per device (multi-GPU = one per device)."""
+MODE_REFERENCE = 0   # FD_ED25519_AMD_MODE_REFERENCE: the reference's verdicts, bit for bit (default)
+MODE_STRICT = 1      # FD_ED25519_AMD_MODE_STRICT: strict RFC 8032 (include/fd_ed25519_amd.h)
 
-    def __init__(self, device=0, batch_max=1 << 16, blob_max=None):
+
+def _check_mode(mode):
+    """A bad mode is refused here as the library refuses it: before any device call."""
+    if mode not in (MODE_REFERENCE, MODE_STRICT):
+        raise EngineError("bad verdict mode %r (MODE_REFERENCE or MODE_STRICT)" % (mode,))
+    return int(mode)
+
+
+class Engine:
+    """fd_ed25519_amd_t: one engine per device (multi-GPU = one per device).
+    mode: MODE_REFERENCE (default) or MODE_STRICT, for every entry point of
+    this engine; set_mode changes it between batches."""
+
+    def __init__(self, device=0, batch_max=1 << 16, blob_max=None, mode=MODE_REFERENCE):
+        _check_mode(mode)
         if blob_max is None:
             blob_max = max(batch_max * 256, MSG_MAX)
         self._h = lib().fd_ed25519_amd_new(int(device), int(batch_max), int(blob_max))
         if not self._h:
             raise EngineError("fd_ed25519_amd_new(device=%d) failed (no HIP device?)" % device)
         self.device = device
+        if mode != MODE_REFERENCE:
+            self.set_mode(mode)
+
+    def set_mode(self, mode):
+        rc = lib().fd_ed25519_amd_set_mode(self._h, int(mode))
+        if rc:
+            raise EngineError("fd_ed25519_amd_set_mode(%r) rc=%d" % (mode, rc))
+
+    @property
+    def mode(self):
+        return int(lib().fd_ed25519_amd_mode(self._h))
 
     def close(self):
         if self._h:
@@ -350,9 +380,11 @@ def shard_range(n, ndev, r):
 class MultiEngine:
     """fd_ed25519_amd_multi_t: one engine + one persistent host thread per
     entry of `devices` (repeats allowed); a batch is split into contiguous
-    shards verified concurrently, no collective."""
+    shards verified concurrently, no collective.  mode: as Engine's, for
+    every engine."""
 
-    def __init__(self, devices, batch_max=1 << 16, blob_max=None):
+    def __init__(self, devices, batch_max=1 << 16, blob_max=None, mode=MODE_REFERENCE):
+        _check_mode(mode)
         if blob_max is None:
             blob_max = max(batch_max * 256, MSG_MAX)
         dv = np.ascontiguousarray(devices, np.int32)
@@ -360,6 +392,13 @@ class MultiEngine:
         if not self._h:
             raise EngineError("fd_ed25519_amd_multi_new(%r) failed" % (list(devices),))
         self.ndev = int(lib().fd_ed25519_amd_multi_ndev(self._h))
+        if mode != MODE_REFERENCE:
+            self.set_mode(mode)
+
+    def set_mode(self, mode):
+        rc = lib().fd_ed25519_amd_multi_set_mode(self._h, int(mode))
+        if rc:
+            raise EngineError("fd_ed25519_amd_multi_set_mode(%r) rc=%d" % (mode, rc))
 
     def close(self):
         if self._h:
@@ -438,23 +477,43 @@ def workspace_footprint(n):
     return int(lib().fd_ed25519_amd_workspace_footprint(int(n)))
 
 
-def verify_dev(n, d_pub, d_sig, d_off, d_sz, d_blob, d_err, d_ws, stream=0):
+def verify_dev(n, d_pub, d_sig, d_off, d_sz, d_blob, d_err, d_ws, stream=0, mode=MODE_REFERENCE):
     """All arguments are device pointers (ints, e.g. torch tensor .data_ptr());
-    enqueued on `stream` (hipStream_t as int), not synchronised."""
-    rc = lib().fd_ed25519_amd_verify_dev(int(n), d_pub, d_sig, d_off, d_sz, d_blob, d_err, d_ws, stream)
+    enqueued on `stream` (hipStream_t as int), not synchronised.  mode:
+    MODE_REFERENCE or MODE_STRICT (fd_ed25519_amd_verify_dev_mode)."""
+    if mode == MODE_REFERENCE:
+        rc = lib().fd_ed25519_amd_verify_dev(int(n), d_pub, d_sig, d_off, d_sz, d_blob, d_err, d_ws, stream)
+    else:
+        rc = lib().fd_ed25519_amd_verify_dev_mode(int(n), d_pub, d_sig, d_off, d_sz, d_blob, d_err, d_ws, stream,
+                                                  int(mode))
     if rc:
         raise EngineError("fd_ed25519_amd_verify_dev rc=%d" % rc)
 
 
-def verify_dev_ev(n, d_pub, d_sig, d_off, d_sz, d_blob, d_err, d_ws, stream, events):
+def verify_dev_ev(n, d_pub, d_sig, d_off, d_sz, d_blob, d_err, d_ws, stream, events, mode=MODE_REFERENCE):
     """verify_dev recording 4 HIP events (hip.Event) around/between the
-    three kernels on `stream`."""
+    three kernels on `stream` (strict mode: k_strict runs before the last)."""
     arr = None
     if events is not None:
         arr = (ctypes.c_void_p * 4)(*[e.handle for e in events])
-    rc = lib().fd_ed25519_amd_verify_dev_ev(int(n), d_pub, d_sig, d_off, d_sz, d_blob, d_err, d_ws, stream, arr)
+    if mode == MODE_REFERENCE:
+        rc = lib().fd_ed25519_amd_verify_dev_ev(int(n), d_pub, d_sig, d_off, d_sz, d_blob, d_err, d_ws, stream, arr)
+    else:
+        rc = lib().fd_ed25519_amd_verify_dev_ev_mode(int(n), d_pub, d_sig, d_off, d_sz, d_blob, d_err, d_ws, stream,
+                                                     arr, int(mode))
     if rc:
         raise EngineError("fd_ed25519_amd_verify_dev_ev rc=%d" % rc)
+
+
+def verify_txns_dev(txn_cnt, slot_cnt, d_payload, d_txn_off, d_txn_sz, d_tbase, d_txn_err, d_sig_err, d_ws,
+                    stream=0, mode=MODE_REFERENCE):
+    """fd_ed25519_amd_verify_txns_dev_mode: the device-resident transaction
+    batch (include/fd_txn_amd.h), device pointers as ints; d_sig_err may be
+    0 / None.  Enqueued on `stream`, not synchronised."""
+    rc = lib().fd_ed25519_amd_verify_txns_dev_mode(int(txn_cnt), int(slot_cnt), d_payload, d_txn_off, d_txn_sz,
+                                                   d_tbase, d_txn_err, d_sig_err, d_ws, stream, int(mode))
+    if rc:
+        raise EngineError("fd_ed25519_amd_verify_txns_dev_mode rc=%d" % rc)
 
 
 def work_stats_dev(n, d_ws, d_stats, stream=0):

@@ -15,7 +15,9 @@
  *
  * Part 2 is new: batch entry points (the reference only verifies one
  * signature per call).  Every verdict they return equals what Part 1's
- * fd_ed25519_verify returns for the same inputs.
+ * fd_ed25519_verify returns for the same inputs -- by default.  An engine
+ * may opt in to strict RFC 8032 verdicts instead (fd_ed25519_amd_set_mode,
+ * FD_ED25519_AMD_MODE_STRICT below).
  *
  * All verify work runs on the GPU.  There is no CPU fallback: without a
  * usable HIP device every verify entry point returns FD_ED25519_AMD_ERR_DEVICE
@@ -148,6 +150,43 @@ fd_ed25519_amd_new( int device, ulong batch_max, ulong blob_max );
 void
 fd_ed25519_amd_delete( fd_ed25519_amd_t * eng );
 
+/* Verdict mode, per engine (no process-wide state; engines are
+   independent).  An engine starts in FD_ED25519_AMD_MODE_REFERENCE: every
+   verdict equals the reference's default build bit for bit, including
+   three behaviours a network-facing caller does not want (DESIGN.md,
+   "Reproduced, not fixed"): s values with s[31]==0x10 and a nonzero byte in
+   s[16..30] are ACCEPTED without looking at A, R or M; small-order and
+   non-canonical points are accepted (A = R = identity, s = 0 verifies any
+   message); and about 1.6e-6 of valid signatures are rejected with -3.
+
+   FD_ED25519_AMD_MODE_STRICT returns the strict RFC 8032 verdict instead,
+   decided in this order for (msg, sig, pub):
+     1. s = LE(sig[32:64]) >= L                        -> FD_ED25519_ERR_SIG
+     2. A = pub or R = sig[0:32]: y = LE(bytes) mod 2^255 >= p, or not on
+        the curve, or x = 0 with the sign bit set, or one of the 8 torsion
+        points ([8]P = identity)                       -> FD_ED25519_ERR_PUBKEY
+     3. [s]B - [h]A != R as points, h = SHA-512(R||A||M) mod L
+                                                       -> FD_ED25519_ERR_MSG
+     4. otherwise                                      -> FD_ED25519_SUCCESS
+   A reference -1 or -2 stays -1 / -2.  The mode applies to every entry
+   point of the engine (verify_batch, verify_soa, verify_soa_registered,
+   verify_txns and the multi-engine forms); the workspace footprint is the
+   same.  It costs one more small kernel per batch (measured in
+   profiles/strict_cost.json).  Not covered: the drop-in fd_ed25519_verify
+   (the reference's API keeps the reference's verdicts) and the streaming
+   verify tile (include/fd_tango_amd.h), which always run in reference mode.
+
+   fd_ed25519_amd_set_mode: FD_ED25519_AMD_OK, or FD_ED25519_AMD_ERR_INVAL
+   for any other mode (nothing touches a device).  Call it between batches.
+   fd_ed25519_amd_mode: the engine's mode. */
+#define FD_ED25519_AMD_MODE_REFERENCE (0)   /* default: the reference's verdicts, bit for bit */
+#define FD_ED25519_AMD_MODE_STRICT    (1)   /* the rule above */
+int
+fd_ed25519_amd_set_mode( fd_ed25519_amd_t * eng, int mode );
+
+int
+fd_ed25519_amd_mode( fd_ed25519_amd_t const * eng );
+
 /* Pointer-array batch (the shape of n independent fd_ed25519_verify
    calls): msg[i] (sz[i] bytes), sig[i] (64 B), pub[i] (32 B) -> err[i]
    in {0,-1,-2,-3}.  Host memory, caller-owned, read-only except err.
@@ -229,6 +268,11 @@ fd_ed25519_amd_multi_delete( fd_ed25519_amd_multi_t * multi );
 ulong
 fd_ed25519_amd_multi_ndev( fd_ed25519_amd_multi_t const * multi );
 
+/* fd_ed25519_amd_set_mode on every engine of the multi engine (between
+   batches).  FD_ED25519_AMD_OK or FD_ED25519_AMD_ERR_INVAL. */
+int
+fd_ed25519_amd_multi_set_mode( fd_ed25519_amd_multi_t * multi, int mode );
+
 /* Shard [lo, hi) of n items that engine r of ndev verifies: lo = n*r/ndev. */
 void
 fd_ed25519_amd_shard_range( ulong n, ulong ndev, ulong r, ulong * lo, ulong * hi );
@@ -295,6 +339,37 @@ fd_ed25519_amd_verify_dev_ev( ulong         n,
                               void *        d_ws,
                               void *        stream,
                               void * const * ev );
+
+/* The two calls above with the verdict mode as an argument (there is no
+   engine to carry it): FD_ED25519_AMD_MODE_REFERENCE is the call above,
+   FD_ED25519_AMD_MODE_STRICT also enqueues the strict overlay kernel after
+   the double-scalar-multiply stage (before ev[3]), which rewrites d_err
+   with the strict verdicts.  Same workspace.  Any other mode:
+   FD_ED25519_AMD_ERR_INVAL, checked first, nothing is enqueued. */
+int
+fd_ed25519_amd_verify_dev_mode( ulong         n,
+                                uchar const * d_pub,
+                                uchar const * d_sig,
+                                uint const *  d_msg_off,
+                                uint const *  d_msg_sz,
+                                uchar const * d_blob,
+                                schar *       d_err,
+                                void *        d_ws,
+                                void *        stream,
+                                int           mode );
+
+int
+fd_ed25519_amd_verify_dev_ev_mode( ulong         n,
+                                   uchar const * d_pub,
+                                   uchar const * d_sig,
+                                   uint const *  d_msg_off,
+                                   uint const *  d_msg_sz,
+                                   uchar const * d_blob,
+                                   schar *       d_err,
+                                   void *        d_ws,
+                                   void *        stream,
+                                   void * const * ev,
+                                   int           mode );
 
 /* Optional per-signature work statistics of the last device-resident call
    on the same workspace: d_stats is planar [3][n] uint (double-scalar-

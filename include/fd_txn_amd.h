@@ -195,6 +195,29 @@ fd_ed25519_amd_verify_txns_dev( ulong         txn_cnt,
                                 void *        d_ws,
                                 void *        stream );
 
+/* Verdict mode of the transaction entry points (fd_ed25519_amd.h,
+   FD_ED25519_AMD_MODE_*).  fd_ed25519_amd_verify_txns and the multi-device
+   form follow their engine's mode (fd_ed25519_amd_set_mode /
+   fd_ed25519_amd_multi_set_mode); the device-resident form takes it as an
+   argument.  In FD_ED25519_AMD_MODE_STRICT every signature gets the strict
+   verdict and the transaction rule is unchanged: the first failing
+   signature's code, so a transaction with an s-window signature or a
+   torsion-point signer is rejected (-1 / -2).  FD_TXN_AMD_ERR_PARSE is the
+   same in both modes.  Any other mode: FD_ED25519_AMD_ERR_INVAL, checked
+   first. */
+int
+fd_ed25519_amd_verify_txns_dev_mode( ulong         txn_cnt,
+                                     ulong         slot_cnt,
+                                     uchar const * d_payload,
+                                     uint const *  d_txn_off,
+                                     uint const *  d_txn_sz,
+                                     uint const *  d_tbase,
+                                     schar *       d_txn_err,
+                                     schar *       d_sig_err,
+                                     void *        d_ws,
+                                     void *        stream,
+                                     int           mode );
+
 /* Workload synthesis (config 4): txn_cnt well-formed legacy / v0
    transactions with nsig_lo..nsig_hi signers (account addresses = the
    next public keys of pub[]) and ~msg_lo..msg_hi-byte messages, capped at

@@ -148,6 +148,44 @@ def base_comb_table():
     return out
 
 
+def fe_sqrt(a):
+    """A square root of a mod p (p = 5 mod 8), or None when a is no square."""
+    a %= P
+    x = pow(a, (P + 3) // 8, P)
+    if (x * x - a) % P:
+        x = x * SQRTM1 % P
+    return x if (x * x - a) % P == 0 else None
+
+
+def torsion_y8():
+    """y of the four points of order 8.  The double of (x, y) on
+    -x^2 + y^2 = 1 + d x^2 y^2 has y' = (y^2 + x^2) / (1 - d x^2 y^2), so the
+    points whose double is (+-sqrt(-1), 0), of order 4, are those with
+    x^2 = -y^2; the curve equation then reads d y^4 + 2 y^2 - 1 = 0, i.e.
+    y^2 = (-1 +- sqrt(1 + d)) / d, for the root that is itself a square.
+    Returns the lesser y (the other is p - y).  Checked by doubling:
+    [4](x, y) = (0, -1), [8](x, y) = (0, 1).  The 8 torsion points then have
+    y in {1, p-1, 0, y8, p-y8} (strict mode's point check)."""
+    ys = set()
+    r = fe_sqrt(1 + D)
+    for t in ((-1 + r) * inv(D) % P, (-1 - r) * inv(D) % P):
+        y = fe_sqrt(t)
+        if y is None:
+            continue
+        x = SQRTM1 * y % P
+        for pt in ((x, y), (x, P - y), (P - x, y), (P - x, P - y)):
+            p4 = edwards_double(edwards_double(pt))
+            assert (-pt[0] * pt[0] + pt[1] * pt[1] - 1 - D * pt[0] * pt[0] * pt[1] * pt[1]) % P == 0
+            assert p4 == (0, P - 1) and edwards_double(p4) == (0, 1)
+        ys.update((y, P - y))
+    assert len(ys) == 2
+    return min(ys)
+
+
+def _words(v):
+    return "{ " + ", ".join("0x%08xu" % ((v >> (32 * k)) & 0xffffffff) for k in range(8)) + " }"
+
+
 def _carr(vals):
     return "{ " + ", ".join(str(v) for v in vals) + " }"
 
@@ -189,6 +227,12 @@ def emit(path, prefix):
         lines.append("")
     lb = L.to_bytes(32, "little")
     lines.append(f"#define {pf}_L_BYTES {{ " + ", ".join("0x%02x" % b for b in lb) + " }")
+    lines.append("")
+    y8 = torsion_y8()
+    lines.append("/* y of the points of order 8 (y8 and p - y8) as 8 little-endian 32-bit words:")
+    lines.append("   with y in {0, 1, p-1} the y of every torsion point (strict mode) */")
+    lines.append(f"#define {pf}_Y8_WORDS  {_words(y8)}")
+    lines.append(f"#define {pf}_Y8N_WORDS {_words(P - y8)}")
     lines.append("")
     lines.append(f"#endif /* {pf}_CONSTS_H */")
     with open(path, "w") as f:
