@@ -47,7 +47,7 @@ enum { OP_D = 0, OP_AA = 1, OP_AB = 2, OP_EMPTY = 3, OP_NONE = 4 };
    their operand with the same code from different bases */
 __device__ i32 g_bi12[8][48];
 #ifdef FD_AMD_DIAG
-__device__ u32 g_pool_dbg[4];   /* steps, live lanes, ADD steps, refill-only steps (summed over waves) */
+__device__ u32 g_pool_dbg[5];   /* steps, live lanes, ADD steps, refill-only steps, ADD-only steps (summed over waves) */
 __device__ u64 g_pool_dbg_t[8192][4];   /* per wave: wall_clock64 at start, at exhaustion of the counter, at exit; steps after exhaustion | lanes << 32 */
 #endif
 
@@ -205,6 +205,78 @@ pool_store_ts( PTR s, u32 stride, p1p1 const & t ) {
 #define FD_POOL_REFILL 8u
 #endif
 
+/* The mixed step's op on one lane's p1p1 state: k_dsm's uniform 8-mul step
+   (p1p1 -> p3, then the ADD's or the DBL's four products as general muls,
+   operands selected per lane).  HAS_DBL false is the same step for a
+   selection that holds no DBL slot: the DBL lane mask is the constant 0, so
+   every select keeps its ADD arm and folds away.  There a dead lane
+   (live false) reads g_bi12[0], as a DBL lane does in the general step; the
+   caller stores nothing for it. */
+template<bool HAS_DBL>
+__device__ __forceinline__ i32 pool_vsel( u64 mD, i32 d, i32 a ) { return HAS_DBL ? vsel( mD, d, a ) : a; }
+
+template<bool HAS_DBL>
+__device__ __forceinline__ void
+pool_mixed_body( p1p1 & t, u32 op, u32 hA, u32 hB, u32 si, bool live, i32 const * Ai ) {
+  bool isadd = HAS_DBL ? (op == OP_AA || op == OP_AB) : live;
+  int dg = (op == OP_AA) ? (int)(i8)(hA >> 8) : (int)(i8)(hB >> 8);
+  bool neg = isadd && dg < 0;
+  int e = isadd ? ((dg < 0 ? -dg : dg) >> 1) & 7 : 0;
+  i32 const * qb = (op == OP_AA) ? Ai + (size_t)si*384u + e*48 : &g_bi12[e][0];
+  int const rowM = neg ? 2 : 1, rowP = neg ? 1 : 2;
+  fe q[4];
+# define Q_ROW( R_, C_ ) do {                                                     \
+    int4 const * src_ = (int4 const *)(qb + (C_)*12);                            \
+    int4 x0 = src_[0], x1 = src_[1], x2 = src_[2];                               \
+    q[R_].v[0] = x0.x; q[R_].v[1] = x0.y; q[R_].v[2] = x0.z; q[R_].v[3] = x0.w;  \
+    q[R_].v[4] = x1.x; q[R_].v[5] = x1.y; q[R_].v[6] = x1.z; q[R_].v[7] = x1.w;  \
+    q[R_].v[8] = x2.x; q[R_].v[9] = x2.y;                                        \
+  } while(0)
+  Q_ROW( 0, 0 ); Q_ROW( 1, rowM ); Q_ROW( 2, rowP ); Q_ROW( 3, 3 );
+# undef Q_ROW
+  p3 u = ge_p1p1_to_p3_fold( t );
+  /* the table operand is first touched here, after p1p1 -> p3 (its x19
+     pre-multiples would otherwise be scheduled first and wait for it) */
+  _Pragma("unroll") for( int r=0; r<4; r++ )
+    asm volatile( "" : "+v"(q[r].v[0]), "+v"(q[r].v[1]), "+v"(q[r].v[2]), "+v"(q[r].v[3]), "+v"(q[r].v[4]),
+                       "+v"(q[r].v[5]), "+v"(q[r].v[6]), "+v"(q[r].v[7]), "+v"(q[r].v[8]), "+v"(q[r].v[9])
+                     : "v"(u.X.v[9]), "v"(u.T.v[9]) );
+  /* k_dsm's op body and mix (see k_dsm) */
+  u64 const mD = HAS_DBL ? __builtin_amdgcn_ballot_w64( !isadd ) : 0UL, mN = __builtin_amdgcn_ballot_w64( neg );
+  fe m0, m1, m2, m3;
+  {
+    fe a0, b0, a1, b1, a2, b2, a3, b3;
+    _Pragma("unroll") for( int k=0; k<10; k++ ) {
+      i32 xy = u.X.v[k] + u.Y.v[k];
+      a0.v[k] = xy;                                                        b0.v[k] = pool_vsel<HAS_DBL>( mD, xy, q[2].v[k] );
+      a1.v[k] = pool_vsel<HAS_DBL>( mD, u.Y.v[k], u.Y.v[k] - u.X.v[k] );   b1.v[k] = pool_vsel<HAS_DBL>( mD, u.Y.v[k], q[1].v[k] );
+      a2.v[k] = u.Z.v[k];                                                  b2.v[k] = pool_vsel<HAS_DBL>( mD, u.Z.v[k] + u.Z.v[k], q[0].v[k] );
+      a3.v[k] = pool_vsel<HAS_DBL>( mD, u.X.v[k], u.T.v[k] );              b3.v[k] = pool_vsel<HAS_DBL>( mD, u.X.v[k], q[3].v[k] );
+    }
+    fe_mul_fold2w<true, true>( m0, a0, b0, m1, a1, b1 );
+    fe_mul_fold2w<false, true>( m2, a2, b2, m3, a3, b3 );
+  }
+  {
+    u64 mS = mD | mN;
+    i32 Dv = pool_vsel<HAS_DBL>( mD, -1, 0 ), Sv = vsel( mS, -1, 0 ), Sn = vsel( mS, 1, 0 );
+    i32 cXe = Dv & (1<<25), cXo = Dv & (1<<24);
+    i32 cZe = pool_vsel<HAS_DBL>( mD, 0, vsel( mN, (1<<25), -(1<<25) ) ), cZo = pool_vsel<HAS_DBL>( mD, 0, vsel( mN, (1<<24), -(1<<24) ) );
+    i32 const nb2e = (i32)fd_opaque( -(2L<<25) ), nb2o = (i32)fd_opaque( -(2L<<24) );   /* SGPR */
+    i32 const sT = pool_vsel<HAS_DBL>( mD, 0, 2 );
+    _Pragma("unroll") for( int k=0; k<10; k++ ) {
+      i32 cX = (k & 1) ? cXo : cXe, cZ = (k & 1) ? cZo : cZe;
+      i32 A0 = m0.v[k], A1 = m1.v[k], A2 = m2.v[k], A3 = m3.v[k];
+      i32 sA3 = fd_xad( A3, Sv, Sn );
+      i32 z2 = A2 + A2;
+      i32 Z = fd_add3( pool_vsel<HAS_DBL>( mD, A1, z2 ), sA3, cZ );
+      t.X.v[k] = HAS_DBL ? fd_add3( A0 - A1, sA3 & Dv, cX ) : A0 - A1;   /* ADD: X = m0 - m1 */
+      t.Y.v[k] = fd_add3s( A1, pool_vsel<HAS_DBL>( mD, A3, A0 ), (k & 1) ? nb2o : nb2e );
+      t.Z.v[k] = Z;
+      t.T.v[k] = (i32)((u32)A2 << (u32)sT) - Z;
+    }
+  }
+}
+
 
 __device__ __forceinline__ u32 lane_rank( u64 m ) {   /* set bits of m below this lane */
   return __builtin_amdgcn_mbcnt_hi( (u32)(m >> 32), __builtin_amdgcn_mbcnt_lo( (u32)m, 0u ) );
@@ -246,7 +318,7 @@ k_dsmp( u32 n, u8 * __restrict__ ws, ws_layout_t L, u64 iter_cap ) {
   if( iter_cap < iter_max ) iter_max = iter_cap;
   bool guard = true;
 #ifdef FD_AMD_DIAG
-  u32 dbg_steps = 0, dbg_lanes = 0, dbg_add = 0, dbg_idle = 0;
+  u32 dbg_steps = 0, dbg_lanes = 0, dbg_add = 0, dbg_idle = 0, dbg_addonly = 0;
 #endif
   for( u64 iter = 0; iter < iter_max; iter++ ) {
     u32 nD = (u32)(__builtin_popcountll( mD0 ) + __builtin_popcountll( mD1 ));
@@ -356,9 +428,10 @@ k_dsmp( u32 n, u8 * __restrict__ ws, ws_layout_t L, u64 iter_cap ) {
       S1 = (sA1 | mD1) & __builtin_amdgcn_ballot_w64( rk1 < 64u );
     }
     bool in0 = __builtin_amdgcn_inverse_ballot_w64( S0 ), in1 = __builtin_amdgcn_inverse_ballot_w64( S1 );
+    bool const hasD = ((S0 & mD0) | (S1 & mD1)) != 0UL;   /* a mixed step without a DBL slot runs the ADD-only body */
     mA0 &= ~S0; mA1 &= ~S1; mD0 &= ~S0; mD1 &= ~S1;
 #ifdef FD_AMD_DIAG
-    dbg_steps++; dbg_lanes += nsel; dbg_add += mixed;
+    dbg_steps++; dbg_lanes += nsel; dbg_add += mixed; dbg_addonly += mixed && !hasD;
     if( dbg_after ) { dbg_sa++; dbg_la += nsel; }
 #endif
     bool live = l < nsel;
@@ -374,74 +447,32 @@ k_dsmp( u32 n, u8 * __restrict__ ws, ws_layout_t L, u64 iter_cap ) {
     u32 hA = m.y & 0xffffu, hB = m.y >> 16;
     int p = (int)(short)(m.z & 0xffffu);
     u32 ja = (m.z >> 16) & 0xffu, jb = m.z >> 24;
-    /* the consumed event's successor (popped after the op): its dword */
-    u32 pidx = (op == OP_AA && ja >= 2u) ? ja - 2u : (op == OP_AB && jb >= 2u) ? 64u + jb - 2u : 0u;
-    bool pop = (op == OP_AA && ja >= 2u) || (op == OP_AB && jb >= 2u);
-    /* lanes that pop nothing read one shared, cache-resident word instead of
-       their own event row (a load under a branch would wait at the join) */
-    u32 const * nha = pop ? (u32 const *)(dig + (size_t)si*128u) + (pidx >> 1) : (u32 const *)&g_bi12[0][0];
-    u32 nh = *nha;
     p1p1 t;
     pool_load_ts( t, &s_t[0][s], P );
 
+    /* the op, then the op stream's advance: pop the consumed event (only an
+       ADD consumes one, so only a mixed step runs the pop path; `mixed` is
+       wave-uniform), then the next op (branch-free: every select is a lane
+       mask) */
+    bool toAA, toAB;
     if( mixed ) {
-      bool isadd = op == OP_AA || op == OP_AB;
-      int dg = (op == OP_AA) ? (int)(i8)(hA >> 8) : (int)(i8)(hB >> 8);
-      bool neg = isadd && dg < 0;
-      int e = isadd ? ((dg < 0 ? -dg : dg) >> 1) & 7 : 0;
-      i32 const * qb = (op == OP_AA) ? Ai + (size_t)si*384u + e*48 : &g_bi12[e][0];
-      int const rowM = neg ? 2 : 1, rowP = neg ? 1 : 2;
-      fe q[4];
-#     define Q_ROW( R_, C_ ) do {                                                     \
-        int4 const * src_ = (int4 const *)(qb + (C_)*12);                            \
-        int4 x0 = src_[0], x1 = src_[1], x2 = src_[2];                               \
-        q[R_].v[0] = x0.x; q[R_].v[1] = x0.y; q[R_].v[2] = x0.z; q[R_].v[3] = x0.w;  \
-        q[R_].v[4] = x1.x; q[R_].v[5] = x1.y; q[R_].v[6] = x1.z; q[R_].v[7] = x1.w;  \
-        q[R_].v[8] = x2.x; q[R_].v[9] = x2.y;                                        \
-      } while(0)
-      Q_ROW( 0, 0 ); Q_ROW( 1, rowM ); Q_ROW( 2, rowP ); Q_ROW( 3, 3 );
-#     undef Q_ROW
-      p3 u = ge_p1p1_to_p3_fold( t );
-      /* the table operand is first touched here, after p1p1 -> p3 (its x19
-         pre-multiples would otherwise be scheduled first and wait for it) */
-      _Pragma("unroll") for( int r=0; r<4; r++ )
-        asm volatile( "" : "+v"(q[r].v[0]), "+v"(q[r].v[1]), "+v"(q[r].v[2]), "+v"(q[r].v[3]), "+v"(q[r].v[4]),
-                           "+v"(q[r].v[5]), "+v"(q[r].v[6]), "+v"(q[r].v[7]), "+v"(q[r].v[8]), "+v"(q[r].v[9])
-                         : "v"(u.X.v[9]), "v"(u.T.v[9]) );
-      /* k_dsm's op body and mix (see k_dsm) */
-      u64 mD = __builtin_amdgcn_ballot_w64( !isadd ), mN = __builtin_amdgcn_ballot_w64( neg );
-      fe m0, m1, m2, m3;
-      {
-        fe a0, b0, a1, b1, a2, b2, a3, b3;
-        _Pragma("unroll") for( int k=0; k<10; k++ ) {
-          i32 xy = u.X.v[k] + u.Y.v[k];
-          a0.v[k] = xy;                                     b0.v[k] = vsel( mD, xy, q[2].v[k] );
-          a1.v[k] = vsel( mD, u.Y.v[k], u.Y.v[k] - u.X.v[k] ); b1.v[k] = vsel( mD, u.Y.v[k], q[1].v[k] );
-          a2.v[k] = u.Z.v[k];                              b2.v[k] = vsel( mD, u.Z.v[k] + u.Z.v[k], q[0].v[k] );
-          a3.v[k] = vsel( mD, u.X.v[k], u.T.v[k] );        b3.v[k] = vsel( mD, u.X.v[k], q[3].v[k] );
-        }
-        fe_mul_fold2w<true, true>( m0, a0, b0, m1, a1, b1 );
-        fe_mul_fold2w<false, true>( m2, a2, b2, m3, a3, b3 );
-      }
-      {
-        u64 mS = mD | mN;
-        i32 Dv = vsel( mD, -1, 0 ), Sv = vsel( mS, -1, 0 ), Sn = vsel( mS, 1, 0 );
-        i32 cXe = Dv & (1<<25), cXo = Dv & (1<<24);
-        i32 cZe = vsel( mD, 0, vsel( mN, (1<<25), -(1<<25) ) ), cZo = vsel( mD, 0, vsel( mN, (1<<24), -(1<<24) ) );
-        i32 const nb2e = (i32)fd_opaque( -(2L<<25) ), nb2o = (i32)fd_opaque( -(2L<<24) );   /* SGPR */
-        i32 const sT = vsel( mD, 0, 2 );
-        _Pragma("unroll") for( int k=0; k<10; k++ ) {
-          i32 cX = (k & 1) ? cXo : cXe, cZ = (k & 1) ? cZo : cZe;
-          i32 A0 = m0.v[k], A1 = m1.v[k], A2 = m2.v[k], A3 = m3.v[k];
-          i32 sA3 = fd_xad( A3, Sv, Sn );
-          i32 z2 = A2 + A2;
-          i32 Z = fd_add3( vsel( mD, A1, z2 ), sA3, cZ );
-          t.X.v[k] = fd_add3( A0 - A1, sA3 & Dv, cX );
-          t.Y.v[k] = fd_add3s( A1, vsel( mD, A3, A0 ), (k & 1) ? nb2o : nb2e );
-          t.Z.v[k] = Z;
-          t.T.v[k] = (i32)((u32)A2 << (u32)sT) - Z;
-        }
-      }
+      /* the consumed event's successor (popped after the op): its dword */
+      u32 pidx = (op == OP_AA && ja >= 2u) ? ja - 2u : (op == OP_AB && jb >= 2u) ? 64u + jb - 2u : 0u;
+      bool pop = (op == OP_AA && ja >= 2u) || (op == OP_AB && jb >= 2u);
+      /* lanes that pop nothing read one shared, cache-resident word instead of
+         their own event row (a load under a divergent branch would wait at
+         the join) */
+      u32 const * nha = pop ? (u32 const *)(dig + (size_t)si*128u) + (pidx >> 1) : (u32 const *)&g_bi12[0][0];
+      u32 nh = *nha;
+      if( hasD ) pool_mixed_body<true>( t, op, hA, hB, si, live, Ai );
+      else       pool_mixed_body<false>( t, op, hA, hB, si, live, Ai );
+      bool const isAA = op == OP_AA, isAB = op == OP_AB, isDb = op == OP_D;
+      u32 ev = __builtin_amdgcn_ubfe( nh, (pidx & 1u) << 4, 16u );
+      ja -= (u32)isAA; jb -= (u32)isAB;
+      hA = isAA ? (ja ? ev : 0xffffu) : hA;
+      hB = isAB ? (jb ? ev : 0xffffu) : hB;
+      toAA = isDb && hA != 0xffffu && (hA & 0xffu) == (u32)p;
+      toAB = !toAA && (isDb || isAA) && hB != 0xffffu && (hB & 0xffu) == (u32)p;
     } else {
       /* p1p1 -> p2 (the first three products of p1p1 -> p3), then the
          doubling (avx/fd_ed25519_ge.c:493-498) with squares */
@@ -459,19 +490,10 @@ k_dsmp( u32 n, u8 * __restrict__ ws, ws_layout_t L, u64 iter_cap ) {
         t.Z.v[k] = z;
         t.T.v[k] = d.v[k] - z;
       }
+      /* every selected slot's op is a doubling: heads and counts stay */
+      toAA = hA != 0xffffu && (hA & 0xffu) == (u32)p;
+      toAB = !toAA && hB != 0xffffu && (hB & 0xffu) == (u32)p;
     }
-
-    /* advance the op stream: pop the consumed event, then the next op
-       (branch-free: every select is a lane mask) */
-    bool const isAA = op == OP_AA, isAB = op == OP_AB, isDb = op == OP_D;
-    {
-      u32 ev = __builtin_amdgcn_ubfe( nh, (pidx & 1u) << 4, 16u );
-      ja -= (u32)isAA; jb -= (u32)isAB;
-      hA = isAA ? (ja ? ev : 0xffffu) : hA;
-      hB = isAB ? (jb ? ev : 0xffffu) : hB;
-    }
-    bool const toAA = isDb && hA != 0xffffu && (hA & 0xffu) == (u32)p;
-    bool const toAB = !toAA && (isDb || isAA) && hB != 0xffffu && (hB & 0xffu) == (u32)p;
     p -= (int)!(toAA || toAB);
     u32 nop = !live ? (u32)OP_EMPTY : toAA ? (u32)OP_AA : toAB ? (u32)OP_AB : (p < 0) ? (u32)OP_EMPTY : (u32)OP_D;
     if( live ) {
@@ -492,7 +514,7 @@ k_dsmp( u32 n, u8 * __restrict__ ws, ws_layout_t L, u64 iter_cap ) {
   }
   if( guard && l == 0u ) atomicOr( (u32 *)(ws + L.ctr) + 1, 1u );
 #ifdef FD_AMD_DIAG
-  if( l == 0u ) { atomicAdd( &g_pool_dbg[0], dbg_steps ); atomicAdd( &g_pool_dbg[1], dbg_lanes ); atomicAdd( &g_pool_dbg[2], dbg_add ); atomicAdd( &g_pool_dbg[3], dbg_idle ); }
+  if( l == 0u ) { atomicAdd( &g_pool_dbg[0], dbg_steps ); atomicAdd( &g_pool_dbg[1], dbg_lanes ); atomicAdd( &g_pool_dbg[2], dbg_add ); atomicAdd( &g_pool_dbg[3], dbg_idle ); atomicAdd( &g_pool_dbg[4], dbg_addonly ); }
   if( l == 0u && w < 8192u ) { g_pool_dbg_t[w][0] = dbg_t0; g_pool_dbg_t[w][1] = dbg_te; g_pool_dbg_t[w][2] = wall_clock64(); g_pool_dbg_t[w][3] = dbg_sa | (dbg_la << 32); }
 #else
   (void)w;
@@ -502,8 +524,8 @@ k_dsmp( u32 n, u8 * __restrict__ ws, ws_layout_t L, u64 iter_cap ) {
 #ifdef FD_AMD_DIAG
 extern "C" int
 fd_amd_pool_debug( unsigned * out, int reset ) {
-  if( hipMemcpyFromSymbol( out, HIP_SYMBOL( g_pool_dbg ), sizeof(unsigned)*4 ) != hipSuccess ) return -1;
-  if( reset ) { unsigned z[4] = { 0, 0, 0, 0 }; if( hipMemcpyToSymbol( HIP_SYMBOL( g_pool_dbg ), z, sizeof(z) ) != hipSuccess ) return -1; }
+  if( hipMemcpyFromSymbol( out, HIP_SYMBOL( g_pool_dbg ), sizeof(unsigned)*5 ) != hipSuccess ) return -1;
+  if( reset ) { unsigned z[5] = { 0, 0, 0, 0, 0 }; if( hipMemcpyToSymbol( HIP_SYMBOL( g_pool_dbg ), z, sizeof(z) ) != hipSuccess ) return -1; }
   return 0;
 }
 extern "C" int

@@ -1,7 +1,10 @@
 """k_dsmp A/B aid: a resident 2^20 batch through the per-lane (k_dsm) and the
 pooled (k_ai + k_dsmp + k_fin) double-scalar multiply, DSM-stage time from
 HIP events, verdicts compared, and the pool's fill statistics when the
-library was built with FD_AMD_DIAG (fd_amd_pool_debug)."""
+library was built with FD_AMD_DIAG (fd_amd_pool_debug): steps, fill, and the
+shares of ADD (mixed) and ADD-only steps.  N=<n> sets the batch size;
+LOCKSTEP=1 replicates the first signature n times (every slot of a pool then
+wants the same op: every ADD step is ADD-only)."""
 import ctypes
 import json
 import os
@@ -13,6 +16,8 @@ from firedancer_amd import ed25519, hip, workload  # noqa: E402
 
 n = int(os.environ.get("N", 1 << 20))
 pub, sig, off, sz, blob = workload.sig_batch(n, 200, 5)
+if os.environ.get("LOCKSTEP"):
+    pub, sig, off = np.repeat(pub[:1], n, axis=0), np.repeat(sig[:1], n, axis=0), np.zeros(n, np.uint32)
 d = {k: hip.DeviceBuffer.from_array(v) for k, v in dict(pub=pub, sig=sig, off=off, sz=sz, blob=blob).items()}
 d_err = hip.DeviceBuffer(n)
 d_ws = hip.DeviceBuffer(ed25519.workspace_footprint(n))
@@ -29,7 +34,7 @@ def run(ev=None):
                           d_ws.ptr, st.handle, ev)
 
 
-res = {"lib": os.path.basename(ed25519.LIB_PATH), "n": n, "waves": os.environ.get("FD_POOL_WAVES")}
+res = {"lib": os.path.basename(ed25519.LIB_PATH), "n": n, "lockstep": bool(os.environ.get("LOCKSTEP")), "waves": os.environ.get("FD_POOL_WAVES")}
 ref = None
 for kern in ("k_dsm", "k_dsmp"):
     ed25519.select_dsm_kernel(kern)
@@ -41,7 +46,7 @@ for kern in ("k_dsm", "k_dsmp"):
     ms = []
     for _ in range(3):
         if dbg:
-            buf = (ctypes.c_uint * 4)()
+            buf = (ctypes.c_uint * 5)()
             dbg(buf, 1)
         ev = [hip.Event() for _ in range(4)]
         run(ev)
@@ -49,11 +54,11 @@ for kern in ("k_dsm", "k_dsmp"):
         ms.append(ev[2].elapsed_ms(ev[3]))
     res[kern] = {"dsm_ms": min(ms), "same": bool(np.array_equal(err, ref))}
     if kern == "k_dsmp" and dbg:
-        buf = (ctypes.c_uint * 4)()
+        buf = (ctypes.c_uint * 5)()
         dbg(buf, 0)
-        steps, lanes, add, idle = list(buf)
+        steps, lanes, add, idle, addonly = list(buf)
         res["pool"] = {"steps": steps, "fill": lanes / max(1, 64 * steps), "add_frac": add / max(1, steps),
-                       "idle": idle}
+                       "idle": idle, "add_only_steps": addonly, "add_only_frac": addonly / max(1, steps)}
         tb = np.zeros((8192, 4), np.uint64)
         if L.fd_amd_pool_debug_times(ctypes.c_void_p(tb.ctypes.data)) == 0:
             W = int(os.environ.get("FD_POOL_WAVES") or 2048)
