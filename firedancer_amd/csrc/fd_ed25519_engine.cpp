@@ -40,17 +40,8 @@
    the streams' commands in order, so a D2H queued behind one batch's
    kernels would hold up the next batch's H2D on another stream. */
 static hipError_t
-slot_out( slot_t * s, void * h_dst, void const * d_src, ulong n ) {
-  void * d_dst = h_dst == (void *)s->h_err  ? s->m_err  :
-                 h_dst == (void *)s->h_terr ? s->m_terr :
-                 h_dst == (void *)s->h_tag  ? s->m_tag  : NULL;
-  if( !d_dst ) return hipErrorInvalidValue;
-  return fd_amd_launch_copy_out( d_dst, d_src, n, s->stream ) ? hipErrorLaunchFailure : hipSuccess;
-}
-
-int
-fd_amd_slot_out( slot_t * s, void * h_dst, void const * d_src, ulong n ) {
-  return slot_out( s, h_dst, d_src, n ) == hipSuccess ? 0 : -1;
+slot_out( slot_t * s, void * m_dst /* s->m_err or s->m_terr */, void const * d_src, ulong n ) {
+  return fd_amd_launch_copy_out( m_dst, d_src, n, s->stream ) ? hipErrorLaunchFailure : hipSuccess;
 }
 
 static void
@@ -62,11 +53,7 @@ slot_free( slot_t * s ) {
   if( s->d_sz   ) (void)hipFree( s->d_sz );
   if( s->d_err  ) (void)hipFree( s->d_err );
   if( s->d_ws   ) (void)hipFree( s->d_ws );
-  if( s->h_pub  ) (void)hipHostFree( s->h_pub );
-  if( s->h_sig  ) (void)hipHostFree( s->h_sig );
   if( s->h_blob ) (void)hipHostFree( s->h_blob );
-  if( s->h_off  ) (void)hipHostFree( s->h_off );
-  if( s->h_sz   ) (void)hipHostFree( s->h_sz );
   if( s->h_err  ) (void)hipHostFree( s->h_err );
   if( s->d_pack ) (void)hipFree( s->d_pack );
   if( s->h_pack ) (void)hipHostFree( s->h_pack );
@@ -80,7 +67,6 @@ slot_free( slot_t * s ) {
   if( s->h_tsz  ) (void)hipHostFree( s->h_tsz );
   if( s->h_tbase) (void)hipHostFree( s->h_tbase );
   if( s->h_terr ) (void)hipHostFree( s->h_terr );
-  if( s->h_tag  ) (void)hipHostFree( s->h_tag );
   if( s->stream ) (void)hipStreamDestroy( s->stream );
   if( s->done   ) (void)hipEventDestroy( s->done );
   memset( s, 0, sizeof(*s) );
@@ -97,11 +83,7 @@ slot_alloc( slot_t * s, ulong cap, ulong blob_cap ) {
   HIPCHK( hipMalloc( (void **)&s->d_sz,   4UL*cap ) );
   HIPCHK( hipMalloc( (void **)&s->d_err,  cap ) );
   HIPCHK( hipMalloc( &s->d_ws, L.total ) );
-  HIPCHK( hipHostMalloc( (void **)&s->h_pub,  32UL*cap, hipHostMallocDefault ) );
-  HIPCHK( hipHostMalloc( (void **)&s->h_sig,  64UL*cap, hipHostMallocDefault ) );
   HIPCHK( hipHostMalloc( (void **)&s->h_blob, blob_cap + 64UL, hipHostMallocDefault ) );
-  HIPCHK( hipHostMalloc( (void **)&s->h_off,  4UL*cap, hipHostMallocDefault ) );
-  HIPCHK( hipHostMalloc( (void **)&s->h_sz,   4UL*cap, hipHostMallocDefault ) );
   HIPCHK( hipHostMalloc( (void **)&s->h_err,  cap, hipHostMallocMapped | hipHostMallocCoherent ) );
   HIPCHK( hipHostGetDevicePointer( &s->m_err, s->h_err, 0 ) );
   HIPCHK( hipMalloc( (void **)&s->d_pack, 104UL*cap + blob_cap + 64UL ) );
@@ -122,12 +104,6 @@ fd_ed25519_amd_new( int device, ulong batch_max, ulong blob_max ) {
   int nslot = 2;
   char const * ev = getenv( "FD_ED25519_AMD_NSLOT" );
   if( ev && atoi( ev ) >= 2 && atoi( ev ) <= FD_AMD_SLOT_MAX ) nslot = atoi( ev );
-  return fd_amd_engine_new( device, batch_max, blob_max, nslot );
-}
-
-fd_ed25519_amd_t *
-fd_amd_engine_new( int device, ulong batch_max, ulong blob_max, int nslot ) {
-  if( nslot < 2 || nslot > FD_AMD_SLOT_MAX ) return NULL;
   if( !batch_max ) batch_max = 1;
   if( batch_max > (1UL<<26) ) return NULL;
   if( blob_max < FD_ED25519_AMD_MSG_MAX ) blob_max = FD_ED25519_AMD_MSG_MAX;
@@ -160,8 +136,9 @@ fd_ed25519_amd_delete( fd_ed25519_amd_t * e ) {
   free( e );
 }
 
-int
-fd_amd_slot_alloc_aux( slot_t * s, ulong cap ) {
+/* The slot's transaction buffers, on its first transaction chunk. */
+static int
+slot_alloc_aux( slot_t * s, ulong cap ) {
   if( s->d_toff ) return FD_ED25519_AMD_OK;
   HIPCHK( hipMalloc( (void **)&s->d_toff,  4UL*cap ) );
   HIPCHK( hipMalloc( (void **)&s->d_tsz,   4UL*cap ) );
@@ -174,14 +151,12 @@ fd_amd_slot_alloc_aux( slot_t * s, ulong cap ) {
   HIPCHK( hipHostMalloc( (void **)&s->h_tbase, 4UL*(cap+1UL), hipHostMallocDefault ) );
   HIPCHK( hipHostMalloc( (void **)&s->h_terr,  cap, hipHostMallocMapped | hipHostMallocCoherent ) );
   HIPCHK( hipHostGetDevicePointer( &s->m_terr, s->h_terr, 0 ) );
-  HIPCHK( hipHostMalloc( (void **)&s->h_tag,   8UL*cap, hipHostMallocMapped | hipHostMallocCoherent ) );
-  HIPCHK( hipHostGetDevicePointer( &s->m_tag, s->h_tag, 0 ) );
   return FD_ED25519_AMD_OK;
 }
 
 /* Wait for a slot's chunk and deliver its verdicts. */
-int
-fd_amd_slot_drain( slot_t * s ) {
+static int
+slot_drain( slot_t * s ) {
   if( !s->busy ) return FD_ED25519_AMD_OK;
   HIPCHK( hipEventSynchronize( s->done ) );
   /* k_dsmp's hang guard marks every verdict of its launch (k_fin) */
@@ -212,8 +187,17 @@ engine_quiesce( fd_ed25519_amd_t * e, int rc ) {
   return rc;
 }
 
-int
-fd_amd_slot_launch_packed( slot_t * s, ulong n, ulong blob_sz, schar * out ) {
+/* The chunk just launched on s is in flight: n verdicts, written to h_err,
+   go to `out` when the slot is drained. */
+static void
+slot_in_flight( slot_t * s, schar * out, ulong n ) {
+  s->out = out; s->n = n; s->busy = 1;
+  s->chk_err = n; s->chk_terr = 0;
+}
+
+/* Chunk of n signatures staged in s->h_pack as [pub 32n | sig 64n | off 4n | sz 4n | blob]. */
+static int
+slot_launch_packed( slot_t * s, ulong n, ulong blob_sz, schar * out ) {
   /* latency path: k_front reads the staging in place over PCIe (one pass,
      ~300 B per signature), which saves the H2D and its launch gap; larger
      batches copy first (their kernels re-read the inputs) */
@@ -227,52 +211,33 @@ fd_amd_slot_launch_packed( slot_t * s, ulong n, ulong blob_sz, schar * out ) {
                             d + 104UL*n, s->d_err, s->d_ws, s->stream, 1, NULL, NULL, 0,
                             lat ? (int8_t *)s->m_err : NULL, s->strict ) )   /* latency path: verdicts written in place */
     return FD_ED25519_AMD_ERR_DEVICE;
-  if( !lat ) HIPCHK( slot_out( s, s->h_err, s->d_err, n ) );
+  if( !lat ) HIPCHK( slot_out( s, s->m_err, s->d_err, n ) );
   HIPCHK( hipEventRecord( s->done, s->stream ) );
-  s->out = out; s->n = n; s->busy = 1; s->want_tag = 0;
-  s->chk_err = n; s->chk_terr = 0;
+  slot_in_flight( s, out, n );
   return FD_ED25519_AMD_OK;
-}
-
-int
-fd_amd_slot_ready( slot_t * s ) {
-  if( !s->busy ) return 1;
-  hipError_t e = hipEventQuery( s->done );
-  if( e == hipSuccess ) return 1;
-  if( e == hipErrorNotReady ) return 0;
-  fprintf( stderr, "fd_ed25519_amd: hipEventQuery failed: %s\n", hipGetErrorString( e ) );
-  return FD_ED25519_AMD_ERR_DEVICE;
 }
 
 /* Launch a staged transaction chunk: c transactions (payload bytes in
    h_blob, rebased offsets in h_toff/h_tsz, signature-slot bases in
-   h_tbase[0..c]), nslot = h_tbase[c] signature slots. */
-int
-fd_amd_slot_launch_txn( slot_t * s, ulong c, ulong nslot, ulong blob_sz, schar * t_out, schar * s_out, int want_tag,
-                        uint8_t const * d_payload ) {
+   h_tbase[0..c]), nslot = h_tbase[c] signature slots.  Per-transaction
+   verdicts land in h_terr, per-signature ones (when s_out) in h_err. */
+static int
+slot_launch_txn( slot_t * s, ulong c, ulong nslot, ulong blob_sz, schar * t_out, schar * s_out ) {
   HIPCHK( hipMemcpyAsync( s->d_toff,  s->h_toff,  4UL*c,        hipMemcpyHostToDevice, s->stream ) );
   HIPCHK( hipMemcpyAsync( s->d_tsz,   s->h_tsz,   4UL*c,        hipMemcpyHostToDevice, s->stream ) );
   HIPCHK( hipMemcpyAsync( s->d_tbase, s->h_tbase, 4UL*(c+1UL),  hipMemcpyHostToDevice, s->stream ) );
-  uint8_t const * pl = d_payload;
-  if( !pl ) {
-    pl = s->d_blob;
-    if( blob_sz ) HIPCHK( hipMemcpyAsync( s->d_blob, s->h_blob, blob_sz, hipMemcpyHostToDevice, s->stream ) );
-  }
-  if( fd_amd_launch_txn_parse( (uint32_t)c, pl, s->d_toff, s->d_tsz, s->d_fp, NULL, 0, s->d_tbase,
+  if( blob_sz ) HIPCHK( hipMemcpyAsync( s->d_blob, s->h_blob, blob_sz, hipMemcpyHostToDevice, s->stream ) );
+  if( fd_amd_launch_txn_parse( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, s->d_fp, NULL, 0, s->d_tbase,
                                s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_skip, s->stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
-  if( nslot && fd_amd_launch_verify( (uint32_t)nslot, s->d_pub, s->d_sig, s->d_off, s->d_sz, pl, s->d_err,
-                                     s->d_ws, s->stream, 0, NULL, s->d_skip, s->dsm_mode, NULL, s->strict ) )
+  if( nslot && fd_amd_launch_verify( (uint32_t)nslot, s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_blob, s->d_err,
+                                     s->d_ws, s->stream, 0, NULL, s->d_skip, 0, NULL, s->strict ) )
     return FD_ED25519_AMD_ERR_DEVICE;
   /* after k_strict (same stream): a transaction's verdict is its first failing signature's code in the engine's mode */
   if( fd_amd_launch_txn_reduce( (uint32_t)c, s->d_fp, s->d_tbase, s->d_err, s->d_terr, s->stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
-  HIPCHK( slot_out( s, s->h_terr, s->d_terr, c ) );
-  if( s_out && nslot ) HIPCHK( slot_out( s, s->h_err, s->d_err, nslot ) );
-  if( want_tag && nslot ) {
-    ws_layout_t L = fd_amd_ws_layout( nslot );
-    HIPCHK( slot_out( s, s->h_tag, (uint8_t *)s->d_ws + L.tag, 8UL*nslot ) );
-  }
+  HIPCHK( slot_out( s, s->m_terr, s->d_terr, c ) );
+  if( s_out && nslot ) HIPCHK( slot_out( s, s->m_err, s->d_err, nslot ) );
   HIPCHK( hipEventRecord( s->done, s->stream ) );
   s->t_out = t_out; s->t_n = c;
   s->s_out = nslot ? s_out : NULL; s->s_n = nslot;
@@ -281,46 +246,26 @@ fd_amd_slot_launch_txn( slot_t * s, ulong c, ulong nslot, ulong blob_sz, schar *
   return FD_ED25519_AMD_OK;
 }
 
-/* Generic chunked, double-buffered driver.  get(i, &msg, &sz, &sig, &pub)
-   returns signature i's inputs. */
-template<typename GET>
+/* The chunk driver of every host batch call: `total` items (signatures or
+   transactions) go through slots [0, ring) round robin.  A slot's previous
+   chunk is drained before the slot is reused; stage( slot, first ) sizes,
+   stages and launches the chunk that starts at item `first` and returns the
+   items it took (> 0; the callers' argument checks see to that) or an error
+   code (< 0); the ring is drained at the end.  Any error quiesces the
+   engine. */
+template<typename STAGE>
 static int
-run_chunked( fd_ed25519_amd_t * e, ulong n, schar * err, GET get ) {
+run_ring( fd_ed25519_amd_t * e, int ring, ulong total, STAGE stage ) {
   if( hipSetDevice( e->device ) != hipSuccess ) return FD_ED25519_AMD_ERR_DEVICE;
-  for( ulong j=0; j<n; j++ ) {          /* every message must fit one chunk: checked before anything launches */
-    uint8_t const * msg; ulong sz; uint8_t const * sig; uint8_t const * pub;
-    get( j, &msg, &sz, &sig, &pub );
-    if( sz > e->blob_cap || (sz && !msg) ) return FD_ED25519_AMD_ERR_INVAL;
-  }
-  ulong i = 0; int k = 0; int rc = FD_ED25519_AMD_OK;
-  while( i < n ) {
+  int rc; int k = 0;
+  for( ulong i=0; i<total; k=(k + 1) % ring ) {
     slot_t * s = &e->slot[k];
-    if( (rc = fd_amd_slot_drain( s )) ) return engine_quiesce( e, rc );
-    /* size the chunk first, then stage it packed: [pub|sig|off|sz|blob] */
-    ulong c = 0, bsz = 0;
-    while( i + c < n && c < e->cap ) {
-      uint8_t const * msg; ulong sz; uint8_t const * sig; uint8_t const * pub;
-      get( i + c, &msg, &sz, &sig, &pub );
-      if( bsz + sz > e->blob_cap ) break;
-      bsz += sz; c++;
-    }
-    uint8_t * hp = s->h_pack;
-    uint8_t * h_pub = hp, * h_sig = hp + 32UL*c, * h_blob = hp + 104UL*c;
-    uint32_t * h_off = (uint32_t *)(hp + 96UL*c), * h_sz = (uint32_t *)(hp + 100UL*c);
-    bsz = 0;
-    for( ulong j=0; j<c; j++ ) {
-      uint8_t const * msg; ulong sz; uint8_t const * sig; uint8_t const * pub;
-      get( i + j, &msg, &sz, &sig, &pub );
-      memcpy( h_pub + 32UL*j, pub, 32 );
-      memcpy( h_sig + 64UL*j, sig, 64 );
-      if( sz ) memcpy( h_blob + bsz, msg, sz );
-      h_off[j] = (uint32_t)bsz; h_sz[j] = (uint32_t)sz;
-      bsz += sz;
-    }
-    if( (rc = fd_amd_slot_launch_packed( s, c, bsz, err + i )) ) return engine_quiesce( e, rc );
-    i += c; k ^= 1;
+    if( (rc = slot_drain( s )) ) return engine_quiesce( e, rc );
+    long c = stage( s, i );
+    if( c < 0L ) return engine_quiesce( e, (int)c );
+    i += (ulong)c;
   }
-  for( int j=0; j<2; j++ ) if( (rc = fd_amd_slot_drain( &e->slot[j] )) ) return engine_quiesce( e, rc );
+  for( int j=0; j<ring; j++ ) if( (rc = slot_drain( &e->slot[j] )) ) return engine_quiesce( e, rc );
   return FD_ED25519_AMD_OK;
 }
 
@@ -328,8 +273,25 @@ extern "C" int
 fd_ed25519_amd_verify_batch( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
                              void const * const * sig, void const * const * pub, schar * err ) {
   if( !e || (n && (!msg || !sz || !sig || !pub || !err)) ) return FD_ED25519_AMD_ERR_INVAL;
-  return run_chunked( e, n, err, [&]( ulong i, uint8_t const ** m, ulong * s, uint8_t const ** g, uint8_t const ** p ) {
-    *m = (uint8_t const *)msg[i]; *s = sz[i]; *g = (uint8_t const *)sig[i]; *p = (uint8_t const *)pub[i];
+  for( ulong j=0; j<n; j++ )            /* every message must fit one chunk: checked before anything launches */
+    if( sz[j] > e->blob_cap || (sz[j] && !msg[j]) ) return FD_ED25519_AMD_ERR_INVAL;
+  return run_ring( e, 2, n, [&]( slot_t * s, ulong i ) -> long {
+    /* size the chunk first, then stage it packed: [pub|sig|off|sz|blob] */
+    ulong c = 0, bsz = 0;
+    while( i + c < n && c < e->cap && bsz + sz[i+c] <= e->blob_cap ) { bsz += sz[i+c]; c++; }
+    uint8_t * hp = s->h_pack;
+    uint8_t * h_pub = hp, * h_sig = hp + 32UL*c, * h_blob = hp + 104UL*c;
+    uint32_t * h_off = (uint32_t *)(hp + 96UL*c), * h_sz = (uint32_t *)(hp + 100UL*c);
+    bsz = 0;
+    for( ulong j=0; j<c; j++ ) {
+      memcpy( h_pub + 32UL*j, pub[i+j], 32 );
+      memcpy( h_sig + 64UL*j, sig[i+j], 64 );
+      if( sz[i+j] ) memcpy( h_blob + bsz, msg[i+j], sz[i+j] );
+      h_off[j] = (uint32_t)bsz; h_sz[j] = (uint32_t)sz[i+j];
+      bsz += sz[i+j];
+    }
+    int rc = slot_launch_packed( s, c, bsz, err + i );
+    return rc ? rc : (long)c;
   } );
 }
 
@@ -350,62 +312,85 @@ copy_par( void * dst, void const * src, ulong sz ) {
   for( int t=1; t<nt; t++ ) if( th[t-1].joinable() ) th[t-1].join();
 }
 
-/* SoA staging with block copies: pub and sig are contiguous per chunk, and
-   when the chunk's messages sit in a window of the blob not much larger
-   than their total size, the window is copied as one block and the offsets
-   rebased (no per-message copy).  Other layouts gather message by message. */
-static int
-run_soa( fd_ed25519_amd_t * e, ulong n, uchar const * pub, uchar const * sig, uint const * msg_off,
-         uint const * msg_sz, uchar const * blob, schar * err ) {
-  if( hipSetDevice( e->device ) != hipSuccess ) return FD_ED25519_AMD_ERR_DEVICE;
-  ulong i = 0; int k = 0; int rc = FD_ED25519_AMD_OK;
-  while( i < n ) {
-    slot_t * s = &e->slot[k];
-    if( (rc = fd_amd_slot_drain( s )) ) return engine_quiesce( e, rc );
-    ulong c = 0, bsz = 0, lo = ~0UL, hi = 0UL;
-    while( i + c < n && c < e->cap ) {
-      ulong sz = msg_sz[i+c];                /* <= blob_cap: checked by the caller */
-      if( bsz + sz > e->blob_cap ) break;
-      if( sz ) { ulong o = msg_off[i+c]; lo = o < lo ? o : lo; hi = o + sz > hi ? o + sz : hi; }
-      bsz += sz; c++;
-    }
-    uint8_t * hp = s->h_pack;
-    uint8_t * h_blob = hp + 104UL*c;
-    uint32_t * h_off = (uint32_t *)(hp + 96UL*c), * h_sz = (uint32_t *)(hp + 100UL*c);
-    copy_par( hp, pub + 32UL*i, 32UL*c );
-    copy_par( hp + 32UL*c, sig + 64UL*i, 64UL*c );
-    memcpy( h_sz, msg_sz + i, 4UL*c );
-    ulong win = hi > lo ? hi - lo : 0UL;
-    if( win <= e->blob_cap && win <= bsz + bsz/4UL + 4096UL ) {
-      copy_par( h_blob, blob + (hi > lo ? lo : 0UL), win );
-      for( ulong j=0; j<c; j++ ) h_off[j] = msg_sz[i+j] ? (uint32_t)(msg_off[i+j] - lo) : 0U;
-      bsz = win;
-    } else {
-      bsz = 0;
-      for( ulong j=0; j<c; j++ ) {
-        ulong sz = msg_sz[i+j];
-        if( sz ) memcpy( h_blob + bsz, blob + msg_off[i+j], sz );
-        h_off[j] = (uint32_t)bsz; bsz += sz;
-      }
-    }
-    if( (rc = fd_amd_slot_launch_packed( s, c, bsz, err + i )) ) return engine_quiesce( e, rc );
-    i += c; k = (k + 1) % e->nslot;
-  }
-  for( int j=0; j<e->nslot; j++ ) if( (rc = fd_amd_slot_drain( &e->slot[j] )) ) return engine_quiesce( e, rc );
+int
+fd_amd_soa_args_check( fd_ed25519_amd_t const * e, ulong n, uchar const * pub, uchar const * sig, uint const * msg_off,
+                       uint const * msg_sz, uchar const * blob, ulong blob_sz, schar const * err ) {
+  if( !e || (n && (!pub || !sig || !msg_off || !msg_sz || !err)) ) return FD_ED25519_AMD_ERR_INVAL;
+  for( ulong i=0; i<n; i++ )
+    if( msg_sz[i] && ((ulong)msg_off[i] + msg_sz[i] > blob_sz || !blob || msg_sz[i] > e->blob_cap) )
+      return FD_ED25519_AMD_ERR_INVAL;
   return FD_ED25519_AMD_OK;
 }
 
+/* One SoA chunk: c signatures from signature i on (up to cap, and blob_cap
+   message bytes), their bsz message bytes, and the window [lo, lo+win) of
+   the blob those span (0, 0: no message bytes).  fit_window: also end the
+   chunk before its window outgrows blob_cap (the registered path copies the
+   window whole into d_blob). */
+struct soa_chunk_t { ulong c, bsz, lo, win; };
+
+static soa_chunk_t
+soa_chunk( fd_ed25519_amd_t const * e, ulong n, ulong i, uint const * msg_off, uint const * msg_sz, bool fit_window ) {
+  ulong c = 0, bsz = 0, lo = ~0UL, hi = 0UL;
+  while( i + c < n && c < e->cap ) {
+    ulong sz = msg_sz[i+c];                  /* <= blob_cap: fd_amd_soa_args_check */
+    if( bsz + sz > e->blob_cap ) break;
+    if( sz ) {
+      ulong o = msg_off[i+c];
+      ulong nlo = o < lo ? o : lo, nhi = o + sz > hi ? o + sz : hi;
+      if( fit_window && nhi - nlo > e->blob_cap ) break;
+      lo = nlo; hi = nhi;
+    }
+    bsz += sz; c++;
+  }
+  return hi > lo ? soa_chunk_t{ c, bsz, lo, hi - lo } : soa_chunk_t{ c, bsz, 0UL, 0UL };
+}
+
+/* Stage chunk ch (pub, sig, msg_off, msg_sz: its first signature's) packed
+   in s->h_pack; returns the blob bytes staged.  pub and sig are contiguous
+   per chunk: block copies.  window: the chunk's window of the blob is
+   copied as one block and the offsets rebased (no per-message copy); else
+   the messages are gathered one by one. */
+static ulong
+soa_stage( slot_t * s, soa_chunk_t ch, uchar const * pub, uchar const * sig, uint const * msg_off, uint const * msg_sz,
+           uchar const * blob, bool window ) {
+  ulong c = ch.c;
+  uint8_t * hp = s->h_pack;
+  uint8_t * h_blob = hp + 104UL*c;
+  uint32_t * h_off = (uint32_t *)(hp + 96UL*c), * h_sz = (uint32_t *)(hp + 100UL*c);
+  copy_par( hp, pub, 32UL*c );
+  copy_par( hp + 32UL*c, sig, 64UL*c );
+  memcpy( h_sz, msg_sz, 4UL*c );
+  if( window ) {
+    copy_par( h_blob, blob + ch.lo, ch.win );
+    for( ulong j=0; j<c; j++ ) h_off[j] = msg_sz[j] ? (uint32_t)(msg_off[j] - ch.lo) : 0U;
+    return ch.win;
+  }
+  ulong b = 0;
+  for( ulong j=0; j<c; j++ ) {
+    ulong sz = msg_sz[j];
+    if( sz ) memcpy( h_blob + b, blob + msg_off[j], sz );
+    h_off[j] = (uint32_t)b; b += sz;
+  }
+  return b;
+}
+
+/* SoA staging: a chunk whose messages sit in a window of the blob not much
+   larger than their total size takes the block copy, other layouts the
+   gather. */
 extern "C" int
 fd_ed25519_amd_verify_soa( fd_ed25519_amd_t * e, ulong n, uchar const * pub, uchar const * sig,
                            uint const * msg_off, uint const * msg_sz, uchar const * blob, ulong blob_sz,
                            schar * err ) {
-  if( !e || (n && (!pub || !sig || !msg_off || !msg_sz || !err)) ) return FD_ED25519_AMD_ERR_INVAL;
-  /* every message in bounds and small enough for one chunk: checked before
-     anything launches, so an error never leaves a chunk in flight */
-  for( ulong i=0; i<n; i++ )
-    if( msg_sz[i] && ((ulong)msg_off[i] + msg_sz[i] > blob_sz || !blob || msg_sz[i] > e->blob_cap) )
-      return FD_ED25519_AMD_ERR_INVAL;
-  return run_soa( e, n, pub, sig, msg_off, msg_sz, blob, err );
+  int rc = fd_amd_soa_args_check( e, n, pub, sig, msg_off, msg_sz, blob, blob_sz, err );
+  if( rc ) return rc;
+  return run_ring( e, e->nslot, n, [&]( slot_t * s, ulong i ) -> long {
+    soa_chunk_t ch = soa_chunk( e, n, i, msg_off, msg_sz, false );
+    bool window = ch.win <= e->blob_cap && ch.win <= ch.bsz + ch.bsz/4UL + 4096UL;
+    ulong b = soa_stage( s, ch, pub + 32UL*i, sig + 64UL*i, msg_off + i, msg_sz + i, blob, window );
+    int rc = slot_launch_packed( s, ch.c, b, err + i );
+    return rc ? rc : (long)ch.c;
+  } );
 }
 
 /* ------------------------------------------------------------------ */
@@ -490,10 +475,9 @@ slot_launch_dma( slot_t * s, ulong c, uchar const * pub, uchar const * sig, uint
   if( fd_amd_launch_verify( (uint32_t)c, s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_blob, s->d_err, s->d_ws, s->stream,
                             1, NULL, NULL, 0, NULL, s->strict ) )
     return FD_ED25519_AMD_ERR_DEVICE;
-  HIPCHK( slot_out( s, s->h_err, s->d_err, c ) );
+  HIPCHK( slot_out( s, s->m_err, s->d_err, c ) );
   HIPCHK( hipEventRecord( s->done, s->stream ) );
-  s->out = out; s->n = c; s->busy = 1; s->want_tag = 0;
-  s->chk_err = c; s->chk_terr = 0;
+  slot_in_flight( s, out, c );
   return FD_ED25519_AMD_OK;
 }
 
@@ -501,10 +485,8 @@ extern "C" int
 fd_ed25519_amd_verify_soa_registered( fd_ed25519_amd_t * e, ulong n, uchar const * pub, uchar const * sig,
                                       uint const * msg_off, uint const * msg_sz, uchar const * blob, ulong blob_sz,
                                       schar * err ) {
-  if( !e || (n && (!pub || !sig || !msg_off || !msg_sz || !err)) ) return FD_ED25519_AMD_ERR_INVAL;
-  for( ulong i=0; i<n; i++ )
-    if( msg_sz[i] && ((ulong)msg_off[i] + msg_sz[i] > blob_sz || !blob || msg_sz[i] > e->blob_cap) )
-      return FD_ED25519_AMD_ERR_INVAL;
+  int rc = fd_amd_soa_args_check( e, n, pub, sig, msg_off, msg_sz, blob, blob_sz, err );
+  if( rc ) return rc;
   if( !n ) return FD_ED25519_AMD_OK;
   void * d[5] = { NULL, NULL, NULL, NULL, NULL };   /* the planes' device addresses */
   if( !host_registered( pub, 32UL*n, &d[0] ) || !host_registered( sig, 64UL*n, &d[1] ) ||
@@ -512,65 +494,31 @@ fd_ed25519_amd_verify_soa_registered( fd_ed25519_amd_t * e, ulong n, uchar const
       (blob && blob_sz && !host_registered( blob, blob_sz, &d[4] )) )
     return FD_ED25519_AMD_ERR_INVAL;
   if( !(blob && blob_sz) ) d[4] = d[0];   /* no message bytes: any valid address */
-  if( hipSetDevice( e->device ) != hipSuccess ) return FD_ED25519_AMD_ERR_DEVICE;
-  int rc = FD_ED25519_AMD_OK;
-  if( n <= e->cap && fd_amd_uses_latency_path( (uint32_t)n, 0 ) ) {
+  if( n <= e->cap && fd_amd_uses_latency_path( (uint32_t)n, 0 ) )
     /* a latency-path batch is read once, by k_front: it reads the caller's
-       registered planes in place over PCIe, with no copy on either side */
-    slot_t * s = &e->slot[0];
-    if( (rc = fd_amd_slot_drain( s )) ) return engine_quiesce( e, rc );
-    /* the DSM kernel (strict mode: k_strict) writes the verdicts into the mapped h_err itself */
-    if( fd_amd_launch_verify( (uint32_t)n, (uint8_t const *)d[0], (uint8_t const *)d[1], (uint32_t const *)d[2],
-                              (uint32_t const *)d[3], (uint8_t const *)d[4], s->d_err, s->d_ws, s->stream, 1, NULL,
-                              NULL, 0, (int8_t *)s->m_err, s->strict ) )
-      return engine_quiesce( e, FD_ED25519_AMD_ERR_DEVICE );
-    if( hipEventRecord( s->done, s->stream ) != hipSuccess ) return engine_quiesce( e, FD_ED25519_AMD_ERR_DEVICE );
-    s->out = err; s->n = n; s->busy = 1; s->want_tag = 0;
-    s->chk_err = n; s->chk_terr = 0;
-    if( (rc = fd_amd_slot_drain( s )) ) return engine_quiesce( e, rc );
-    return FD_ED25519_AMD_OK;
-  }
-  ulong i = 0; int k = 0;
-  while( i < n ) {
-    slot_t * s = &e->slot[k];
-    if( (rc = fd_amd_slot_drain( s )) ) return engine_quiesce( e, rc );
-    ulong c = 0, bsz = 0, lo = ~0UL, hi = 0UL;
-    while( i + c < n && c < e->cap ) {
-      ulong sz = msg_sz[i+c];
-      if( bsz + sz > e->blob_cap ) break;
-      if( sz ) {
-        ulong o = msg_off[i+c];
-        ulong nlo = o < lo ? o : lo, nhi = o + sz > hi ? o + sz : hi;
-        if( nhi - nlo > e->blob_cap ) break;     /* the window must fit the device blob */
-        lo = nlo; hi = nhi;
-      }
-      bsz += sz; c++;
-    }
-    ulong win = hi > lo ? hi - lo : 0UL;
-    if( win <= bsz + bsz/4UL + 4096UL ) {
-      rc = slot_launch_dma( s, c, pub + 32UL*i, sig + 64UL*i, msg_off + i, msg_sz + i, blob + (win ? lo : 0UL), win,
-                            (uint)(win ? lo : 0UL), err + i );
-    } else {
-      /* scattered messages: gather them through the pinned staging */
-      uint8_t * hp = s->h_pack;
-      uint8_t * h_blob = hp + 104UL*c;
-      uint32_t * h_off = (uint32_t *)(hp + 96UL*c), * h_sz = (uint32_t *)(hp + 100UL*c);
-      memcpy( hp, pub + 32UL*i, 32UL*c );
-      memcpy( hp + 32UL*c, sig + 64UL*i, 64UL*c );
-      memcpy( h_sz, msg_sz + i, 4UL*c );
-      ulong b = 0;
-      for( ulong j=0; j<c; j++ ) {
-        ulong sz = msg_sz[i+j];
-        if( sz ) memcpy( h_blob + b, blob + msg_off[i+j], sz );
-        h_off[j] = (uint32_t)b; b += sz;
-      }
-      rc = fd_amd_slot_launch_packed( s, c, b, err + i );
-    }
-    if( rc ) return engine_quiesce( e, rc );
-    i += c; k = (k + 1) % e->nslot;
-  }
-  for( int j=0; j<e->nslot; j++ ) if( (rc = fd_amd_slot_drain( &e->slot[j] )) ) return engine_quiesce( e, rc );
-  return FD_ED25519_AMD_OK;
+       registered planes in place over PCIe, with no copy on either side --
+       one chunk on a ring of one slot */
+    return run_ring( e, 1, n, [&]( slot_t * s, ulong ) -> long {
+      /* the DSM kernel (strict mode: k_strict) writes the verdicts into the mapped h_err itself */
+      if( fd_amd_launch_verify( (uint32_t)n, (uint8_t const *)d[0], (uint8_t const *)d[1], (uint32_t const *)d[2],
+                                (uint32_t const *)d[3], (uint8_t const *)d[4], s->d_err, s->d_ws, s->stream, 1, NULL,
+                                NULL, 0, (int8_t *)s->m_err, s->strict ) )
+        return FD_ED25519_AMD_ERR_DEVICE;
+      if( hipEventRecord( s->done, s->stream ) != hipSuccess ) return FD_ED25519_AMD_ERR_DEVICE;
+      slot_in_flight( s, err, n );
+      return (long)n;
+    } );
+  return run_ring( e, e->nslot, n, [&]( slot_t * s, ulong i ) -> long {
+    soa_chunk_t ch = soa_chunk( e, n, i, msg_off, msg_sz, true );
+    int rc;
+    if( ch.win <= ch.bsz + ch.bsz/4UL + 4096UL )
+      rc = slot_launch_dma( s, ch.c, pub + 32UL*i, sig + 64UL*i, msg_off + i, msg_sz + i, blob + ch.lo, ch.win,
+                            (uint)ch.lo, err + i );
+    else   /* scattered messages: gather them through the pinned staging */
+      rc = slot_launch_packed( s, ch.c, soa_stage( s, ch, pub + 32UL*i, sig + 64UL*i, msg_off + i, msg_sz + i, blob, false ),
+                               err + i );
+    return rc ? rc : (long)ch.c;
+  } );
 }
 
 /* Signature slots the engine reserves for a payload: its first byte when
@@ -583,32 +531,31 @@ fd_amd_txn_slots1( uchar const * p, ulong sz ) {
   return ( k >= 1UL && k <= FD_TXN_SIG_MAX && 64UL*k <= sz - 1UL ) ? k : 0UL;
 }
 
-extern "C" int
-fd_ed25519_amd_verify_txns( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
-                            uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err ) {
+int
+fd_amd_txn_args_check( fd_ed25519_amd_t const * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
+                       uint const * txn_sz, ulong payload_sz, schar const * txn_err, uint const * sig_base,
+                       schar const * sig_err ) {
   if( !e || (txn_cnt && (!payload || !txn_off || !txn_sz || !txn_err)) ) return FD_ED25519_AMD_ERR_INVAL;
   if( sig_err && !sig_base ) return FD_ED25519_AMD_ERR_INVAL;
-  /* every transaction in bounds and stageable in one chunk (its bytes in
-     blob_max, its signatures in batch_max): checked before anything
-     launches, so the chunk loop always makes progress */
   for( ulong t=0; t<txn_cnt; t++ ) {
     if( txn_sz[t] > FD_TXN_AMD_MTU || (ulong)txn_off[t] + txn_sz[t] > payload_sz || txn_sz[t] > e->blob_cap )
       return FD_ED25519_AMD_ERR_INVAL;
     if( fd_amd_txn_slots1( payload + txn_off[t], txn_sz[t] ) > e->cap ) return FD_ED25519_AMD_ERR_INVAL;
   }
-  if( hipSetDevice( e->device ) != hipSuccess ) return FD_ED25519_AMD_ERR_DEVICE;
-  int rc;
-  for( int k=0; k<2; k++ ) if( (rc = fd_amd_slot_alloc_aux( &e->slot[k], e->cap )) ) return rc;
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" int
+fd_ed25519_amd_verify_txns( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
+                            uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err ) {
+  int rc = fd_amd_txn_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err );
+  if( rc ) return rc;
   /* global signature numbering (the caller-visible sig_base) */
-  uint acc = 0U;
-  if( sig_base ) {
-    for( ulong t=0; t<txn_cnt; t++ ) { sig_base[t] = acc; acc += (uint)fd_amd_txn_slots1( payload + txn_off[t], txn_sz[t] ); }
-    sig_base[txn_cnt] = acc;
-  }
-  ulong t = 0, gsig = 0; int k = 0;
-  while( t < txn_cnt ) {
-    slot_t * s = &e->slot[k];
-    if( (rc = fd_amd_slot_drain( s )) ) return engine_quiesce( e, rc );
+  if( sig_base ) fd_ed25519_amd_txn_slots( txn_cnt, payload, txn_off, txn_sz, sig_base );
+  ulong gsig = 0;
+  return run_ring( e, 2, txn_cnt, [&]( slot_t * s, ulong t ) -> long {
+    int rc = slot_alloc_aux( s, e->cap );
+    if( rc ) return rc;
     ulong c = 0, bsz = 0, ns = 0;
     while( t + c < txn_cnt && c < e->cap ) {
       uchar const * p = payload + txn_off[t+c];
@@ -619,12 +566,10 @@ fd_ed25519_amd_verify_txns( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * p
       bsz += sz; ns += k2; c++;
     }
     s->h_tbase[c] = (uint32_t)ns;
-    if( (rc = fd_amd_slot_launch_txn( s, c, ns, bsz, txn_err + t, sig_err ? sig_err + gsig : NULL, 0, NULL )) )
-      return engine_quiesce( e, rc );
-    t += c; gsig += ns; k ^= 1;
-  }
-  for( int j=0; j<2; j++ ) if( (rc = fd_amd_slot_drain( &e->slot[j] )) ) return engine_quiesce( e, rc );
-  return FD_ED25519_AMD_OK;
+    rc = slot_launch_txn( s, c, ns, bsz, txn_err + t, sig_err ? sig_err + gsig : NULL );
+    gsig += ns;
+    return rc ? rc : (long)c;
+  } );
 }
 
 /* Device-resident transaction batch: workspace = verify workspace for
@@ -673,7 +618,7 @@ extern "C" int
 fd_ed25519_amd_verify_txns_dev_mode( ulong txn_cnt, ulong slot_cnt, uchar const * d_payload, uint const * d_txn_off,
                                      uint const * d_txn_sz, uint const * d_tbase, schar * d_txn_err, schar * d_sig_err,
                                      void * d_ws, void * stream, int mode ) {
-  if( mode != FD_ED25519_AMD_MODE_REFERENCE && mode != FD_ED25519_AMD_MODE_STRICT ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !fd_amd_mode_ok( mode ) ) return FD_ED25519_AMD_ERR_INVAL;
   if( txn_cnt > 0xFFFFFFFFUL || slot_cnt > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
   if( !txn_cnt ) return FD_ED25519_AMD_OK;
   if( !d_payload || !d_txn_off || !d_txn_sz || !d_tbase || !d_txn_err || !d_ws ) return FD_ED25519_AMD_ERR_INVAL;
@@ -724,16 +669,11 @@ fd_ed25519_amd_workspace_footprint( ulong n ) {
   return fd_amd_ws_layout( n ).total;
 }
 
-static inline bool
-mode_ok( int mode ) {
-  return mode == FD_ED25519_AMD_MODE_REFERENCE || mode == FD_ED25519_AMD_MODE_STRICT;
-}
-
 extern "C" int
 fd_ed25519_amd_verify_dev_ev_mode( ulong n, uchar const * d_pub, uchar const * d_sig, uint const * d_msg_off,
                                    uint const * d_msg_sz, uchar const * d_blob, schar * d_err, void * d_ws,
                                    void * stream, void * const * ev, int mode ) {
-  if( !mode_ok( mode ) ) return FD_ED25519_AMD_ERR_INVAL;   /* before anything touches a device */
+  if( !fd_amd_mode_ok( mode ) ) return FD_ED25519_AMD_ERR_INVAL;   /* before anything touches a device */
   if( n > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
   if( !n ) return FD_ED25519_AMD_OK;
   if( !d_pub || !d_sig || !d_msg_off || !d_msg_sz || !d_blob || !d_err || !d_ws ) return FD_ED25519_AMD_ERR_INVAL;
@@ -770,7 +710,7 @@ fd_ed25519_amd_verify_dev_ev( ulong n, uchar const * d_pub, uchar const * d_sig,
    Calls are synchronous (each drains its chunks), so none is in flight. */
 extern "C" int
 fd_ed25519_amd_set_mode( fd_ed25519_amd_t * e, int mode ) {
-  if( !e || !mode_ok( mode ) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !e || !fd_amd_mode_ok( mode ) ) return FD_ED25519_AMD_ERR_INVAL;
   e->mode = mode;
   for( int k=0; k<FD_AMD_SLOT_MAX; k++ ) e->slot[k].strict = mode == FD_ED25519_AMD_MODE_STRICT;
   return FD_ED25519_AMD_OK;

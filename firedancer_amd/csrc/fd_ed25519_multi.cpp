@@ -129,7 +129,7 @@ fd_ed25519_amd_multi_ndev( fd_ed25519_amd_multi_t const * m ) {
    under run_all's lock. */
 extern "C" int
 fd_ed25519_amd_multi_set_mode( fd_ed25519_amd_multi_t * m, int mode ) {
-  if( !m || (mode != FD_ED25519_AMD_MODE_REFERENCE && mode != FD_ED25519_AMD_MODE_STRICT) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !m || !fd_amd_mode_ok( mode ) ) return FD_ED25519_AMD_ERR_INVAL;
   std::lock_guard<std::mutex> lk( m->mu );
   for( auto * e : m->eng ) if( fd_ed25519_amd_set_mode( e, mode ) ) return FD_ED25519_AMD_ERR_INVAL;
   return FD_ED25519_AMD_OK;
@@ -139,11 +139,8 @@ extern "C" int
 fd_ed25519_amd_multi_verify_soa(fd_ed25519_amd_multi_t * m, ulong n, uchar const * pub, uchar const * sig,
                                  uint const * msg_off, uint const * msg_sz, uchar const * blob, ulong blob_sz,
                                  schar * err ) {
-  if( !m || (n && (!pub || !sig || !msg_off || !msg_sz || !err)) ) return FD_ED25519_AMD_ERR_INVAL;
   /* validated once for the whole batch, so either every shard runs or none */
-  ulong cap = m->eng[0]->blob_cap;
-  for( ulong i=0; i<n; i++ )
-    if( msg_sz[i] && ((ulong)msg_off[i] + msg_sz[i] > blob_sz || !blob || msg_sz[i] > cap) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !m || fd_amd_soa_args_check( m->eng[0], n, pub, sig, msg_off, msg_sz, blob, blob_sz, err ) ) return FD_ED25519_AMD_ERR_INVAL;
   if( !n ) return FD_ED25519_AMD_OK;
   return run_all( m, [&]( ulong r ) -> int {
     ulong lo, hi;
@@ -158,14 +155,8 @@ extern "C" int
 fd_ed25519_amd_multi_verify_txns( fd_ed25519_amd_multi_t * m, ulong txn_cnt, uchar const * payload, uint const * txn_off,
                                   uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base,
                                   schar * sig_err ) {
-  if( !m || (txn_cnt && (!payload || !txn_off || !txn_sz || !txn_err)) ) return FD_ED25519_AMD_ERR_INVAL;
-  if( sig_err && !sig_base ) return FD_ED25519_AMD_ERR_INVAL;
-  fd_ed25519_amd_t const * e0 = m->eng[0];
-  for( ulong t=0; t<txn_cnt; t++ ) {
-    if( txn_sz[t] > FD_TXN_AMD_MTU || (ulong)txn_off[t] + txn_sz[t] > payload_sz || txn_sz[t] > e0->blob_cap )
-      return FD_ED25519_AMD_ERR_INVAL;
-    if( fd_amd_txn_slots1( payload + txn_off[t], txn_sz[t] ) > e0->cap ) return FD_ED25519_AMD_ERR_INVAL;
-  }
+  if( !m || fd_amd_txn_args_check( m->eng[0], txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err ) )
+    return FD_ED25519_AMD_ERR_INVAL;
   if( sig_base ) fd_ed25519_amd_txn_slots( txn_cnt, payload, txn_off, txn_sz, sig_base );   /* global numbering */
   if( !txn_cnt ) return FD_ED25519_AMD_OK;
   return run_all( m, [&]( ulong r ) -> int {
