@@ -67,6 +67,7 @@ slot_free( slot_t * s ) {
   if( s->h_tsz  ) (void)hipHostFree( s->h_tsz );
   if( s->h_tbase) (void)hipHostFree( s->h_tbase );
   if( s->h_terr ) (void)hipHostFree( s->h_terr );
+  if( s->h_tag  ) (void)hipHostFree( s->h_tag );
   if( s->stream ) (void)hipStreamDestroy( s->stream );
   if( s->done   ) (void)hipEventDestroy( s->done );
   memset( s, 0, sizeof(*s) );
@@ -154,7 +155,32 @@ slot_alloc_aux( slot_t * s, ulong cap ) {
   return FD_ED25519_AMD_OK;
 }
 
-/* Wait for a slot's chunk and deliver its verdicts. */
+/* The slot's tag buffers, on the first chunk whose caller asked for tags. */
+static int
+slot_alloc_tag( slot_t * s, ulong cap ) {
+  if( s->h_tag ) return FD_ED25519_AMD_OK;
+  HIPCHK( hipHostMalloc( (void **)&s->h_tag, 16UL*cap, hipHostMallocMapped | hipHostMallocCoherent ) );
+  HIPCHK( hipHostGetDevicePointer( &s->m_tag, s->h_tag, 0 ) );
+  s->h_ttag = s->h_tag + cap;
+  s->m_ttag = (ulong *)s->m_tag + cap;
+  return FD_ED25519_AMD_OK;
+}
+
+/* The n tags of the chunk just verified on s (the tag plane of its
+   workspace) into h_tag, on the slot's stream: k_tag_out writes the mapped
+   buffer, on every path, as slot_out does the verdicts and for its reason.
+   A D2H copy of the plane instead, measured on the throughput path (a 2^20 x
+   200 B verify_soa, 16 chunks): +2.2 to +2.6 ms per call, 9-10 %, behind the
+   other slot's H2D; the kernel: within the untagged calls' spread
+   (profiles/tag_copy_ab.txt). */
+static int
+slot_tags( slot_t * s, ulong n ) {
+  return fd_amd_launch_tag_out( s->m_tag, s->d_ws, n, s->stream ) ? FD_ED25519_AMD_ERR_DEVICE : FD_ED25519_AMD_OK;
+}
+
+/* Wait for a slot's chunk and deliver its verdicts and, where the caller
+   asked for them, its tags: one place, so that draining a slot before it is
+   reused covers both outputs. */
 static int
 slot_drain( slot_t * s ) {
   if( !s->busy ) return FD_ED25519_AMD_OK;
@@ -167,37 +193,43 @@ slot_drain( slot_t * s ) {
     if( s->out   ) memcpy( s->out,   s->h_err,  s->n );
     if( s->t_out ) memcpy( s->t_out, s->h_terr, s->t_n );
     if( s->s_out ) memcpy( s->s_out, s->h_err,  s->s_n );
+    if( s->g_out  ) memcpy( s->g_out,  s->h_tag,  8UL*s->g_n );
+    if( s->tg_out ) memcpy( s->tg_out, s->h_ttag, 8UL*s->tg_n );
   }
   s->out = s->t_out = s->s_out = NULL;
+  s->g_out = s->tg_out = NULL;
   s->busy = 0;
   return fault ? FD_ED25519_AMD_ERR_DEVICE : FD_ED25519_AMD_OK;
 }
 
 /* Error exit of a batch call: wait for every chunk still in flight and
-   forget where its verdicts were to go, so no later call writes into the
-   caller's (by then possibly freed) output arrays. */
+   forget where its verdicts and tags were to go, so no later call writes
+   into the caller's (by then possibly freed) output arrays. */
 static int
 engine_quiesce( fd_ed25519_amd_t * e, int rc ) {
   for( int k=0; k<FD_AMD_SLOT_MAX; k++ ) {
     slot_t * s = &e->slot[k];
     if( s->busy ) (void)hipEventSynchronize( s->done );
     s->out = s->t_out = s->s_out = NULL;
+    s->g_out = s->tg_out = NULL;
     s->busy = 0;
   }
   return rc;
 }
 
 /* The chunk just launched on s is in flight: n verdicts, written to h_err,
-   go to `out` when the slot is drained. */
+   go to `out` when the slot is drained; with tag != NULL its n tags, written
+   to h_tag, go to `tag`. */
 static void
-slot_in_flight( slot_t * s, schar * out, ulong n ) {
+slot_in_flight( slot_t * s, schar * out, ulong * tag, ulong n ) {
   s->out = out; s->n = n; s->busy = 1;
   s->chk_err = n; s->chk_terr = 0;
+  s->g_out = tag; s->g_n = n;
 }
 
 /* Chunk of n signatures staged in s->h_pack as [pub 32n | sig 64n | off 4n | sz 4n | blob]. */
 static int
-slot_launch_packed( slot_t * s, ulong n, ulong blob_sz, schar * out ) {
+slot_launch_packed( slot_t * s, ulong n, ulong blob_sz, schar * out, ulong * tag ) {
   /* latency path: k_front reads the staging in place over PCIe (one pass,
      ~300 B per signature), which saves the H2D and its launch gap; larger
      batches copy first (their kernels re-read the inputs) */
@@ -212,17 +244,25 @@ slot_launch_packed( slot_t * s, ulong n, ulong blob_sz, schar * out ) {
                             lat ? (int8_t *)s->m_err : NULL, s->strict ) )   /* latency path: verdicts written in place */
     return FD_ED25519_AMD_ERR_DEVICE;
   if( !lat ) HIPCHK( slot_out( s, s->m_err, s->d_err, n ) );
+  /* latency path: k_tag_out after the DSM kernel.  The stream is in order
+     and the host waits for one event behind both outputs, so either side of
+     the DSM kernel costs the same one launch; after it, the verify launch
+     sequence is the untagged call's */
+  if( tag && slot_tags( s, n ) ) return FD_ED25519_AMD_ERR_DEVICE;
   HIPCHK( hipEventRecord( s->done, s->stream ) );
-  slot_in_flight( s, out, n );
+  slot_in_flight( s, out, tag, n );
   return FD_ED25519_AMD_OK;
 }
 
 /* Launch a staged transaction chunk: c transactions (payload bytes in
    h_blob, rebased offsets in h_toff/h_tsz, signature-slot bases in
    h_tbase[0..c]), nslot = h_tbase[c] signature slots.  Per-transaction
-   verdicts land in h_terr, per-signature ones (when s_out) in h_err. */
+   verdicts land in h_terr, per-signature ones (when s_out) in h_err; the
+   per-transaction tags (when tt_out) in h_ttag, the per-signature ones (when
+   st_out) in h_tag. */
 static int
-slot_launch_txn( slot_t * s, ulong c, ulong nslot, ulong blob_sz, schar * t_out, schar * s_out ) {
+slot_launch_txn( slot_t * s, ulong c, ulong nslot, ulong blob_sz, schar * t_out, schar * s_out, ulong * tt_out,
+                 ulong * st_out ) {
   HIPCHK( hipMemcpyAsync( s->d_toff,  s->h_toff,  4UL*c,        hipMemcpyHostToDevice, s->stream ) );
   HIPCHK( hipMemcpyAsync( s->d_tsz,   s->h_tsz,   4UL*c,        hipMemcpyHostToDevice, s->stream ) );
   HIPCHK( hipMemcpyAsync( s->d_tbase, s->h_tbase, 4UL*(c+1UL),  hipMemcpyHostToDevice, s->stream ) );
@@ -238,7 +278,12 @@ slot_launch_txn( slot_t * s, ulong c, ulong nslot, ulong blob_sz, schar * t_out,
     return FD_ED25519_AMD_ERR_DEVICE;
   HIPCHK( slot_out( s, s->m_terr, s->d_terr, c ) );
   if( s_out && nslot ) HIPCHK( slot_out( s, s->m_err, s->d_err, nslot ) );
+  /* tags: per transaction its first slot's (no slot launched: no workspace is read), per signature the plane */
+  if( tt_out && fd_amd_launch_tag_gather( s->m_ttag, s->d_ws, (uint32_t)c, s->d_tbase, s->stream ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  if( st_out && nslot && slot_tags( s, nslot ) ) return FD_ED25519_AMD_ERR_DEVICE;
   HIPCHK( hipEventRecord( s->done, s->stream ) );
+  s->tg_out = tt_out; s->tg_n = c;
+  s->g_out = nslot ? st_out : NULL; s->g_n = nslot;
   s->t_out = t_out; s->t_n = c;
   s->s_out = nslot ? s_out : NULL; s->s_n = nslot;
   s->chk_err = (s_out && nslot) ? nslot : 0; s->chk_terr = c;
@@ -272,10 +317,17 @@ run_ring( fd_ed25519_amd_t * e, int ring, ulong total, STAGE stage ) {
 extern "C" int
 fd_ed25519_amd_verify_batch( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
                              void const * const * sig, void const * const * pub, schar * err ) {
+  return fd_ed25519_amd_verify_batch_tag( e, n, msg, sz, sig, pub, err, NULL );
+}
+
+extern "C" int
+fd_ed25519_amd_verify_batch_tag( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
+                                 void const * const * sig, void const * const * pub, schar * err, ulong * tag ) {
   if( !e || (n && (!msg || !sz || !sig || !pub || !err)) ) return FD_ED25519_AMD_ERR_INVAL;
   for( ulong j=0; j<n; j++ )            /* every message must fit one chunk: checked before anything launches */
     if( sz[j] > e->blob_cap || (sz[j] && !msg[j]) ) return FD_ED25519_AMD_ERR_INVAL;
   return run_ring( e, 2, n, [&]( slot_t * s, ulong i ) -> long {
+    if( tag ) { int rc = slot_alloc_tag( s, e->cap ); if( rc ) return rc; }
     /* size the chunk first, then stage it packed: [pub|sig|off|sz|blob] */
     ulong c = 0, bsz = 0;
     while( i + c < n && c < e->cap && bsz + sz[i+c] <= e->blob_cap ) { bsz += sz[i+c]; c++; }
@@ -290,7 +342,7 @@ fd_ed25519_amd_verify_batch( fd_ed25519_amd_t * e, ulong n, void const * const *
       h_off[j] = (uint32_t)bsz; h_sz[j] = (uint32_t)sz[i+j];
       bsz += sz[i+j];
     }
-    int rc = slot_launch_packed( s, c, bsz, err + i );
+    int rc = slot_launch_packed( s, c, bsz, err + i, tag ? tag + i : NULL );
     return rc ? rc : (long)c;
   } );
 }
@@ -382,13 +434,21 @@ extern "C" int
 fd_ed25519_amd_verify_soa( fd_ed25519_amd_t * e, ulong n, uchar const * pub, uchar const * sig,
                            uint const * msg_off, uint const * msg_sz, uchar const * blob, ulong blob_sz,
                            schar * err ) {
+  return fd_ed25519_amd_verify_soa_tag( e, n, pub, sig, msg_off, msg_sz, blob, blob_sz, err, NULL );
+}
+
+extern "C" int
+fd_ed25519_amd_verify_soa_tag( fd_ed25519_amd_t * e, ulong n, uchar const * pub, uchar const * sig,
+                               uint const * msg_off, uint const * msg_sz, uchar const * blob, ulong blob_sz,
+                               schar * err, ulong * tag ) {
   int rc = fd_amd_soa_args_check( e, n, pub, sig, msg_off, msg_sz, blob, blob_sz, err );
   if( rc ) return rc;
   return run_ring( e, e->nslot, n, [&]( slot_t * s, ulong i ) -> long {
+    if( tag ) { int rc = slot_alloc_tag( s, e->cap ); if( rc ) return rc; }
     soa_chunk_t ch = soa_chunk( e, n, i, msg_off, msg_sz, false );
     bool window = ch.win <= e->blob_cap && ch.win <= ch.bsz + ch.bsz/4UL + 4096UL;
     ulong b = soa_stage( s, ch, pub + 32UL*i, sig + 64UL*i, msg_off + i, msg_sz + i, blob, window );
-    int rc = slot_launch_packed( s, ch.c, b, err + i );
+    int rc = slot_launch_packed( s, ch.c, b, err + i, tag ? tag + i : NULL );
     return rc ? rc : (long)ch.c;
   } );
 }
@@ -465,7 +525,7 @@ host_registered( void const * p, ulong sz, void ** dev ) {
    device planes, offsets rebased on the device. */
 static int
 slot_launch_dma( slot_t * s, ulong c, uchar const * pub, uchar const * sig, uint const * off, uint const * sz,
-                 uchar const * win_src, ulong win, uint lo, schar * out ) {
+                 uchar const * win_src, ulong win, uint lo, schar * out, ulong * tag ) {
   HIPCHK( hipMemcpyAsync( s->d_pub, pub, 32UL*c, hipMemcpyHostToDevice, s->stream ) );
   HIPCHK( hipMemcpyAsync( s->d_sig, sig, 64UL*c, hipMemcpyHostToDevice, s->stream ) );
   HIPCHK( hipMemcpyAsync( s->d_off, off, 4UL*c,  hipMemcpyHostToDevice, s->stream ) );
@@ -476,8 +536,9 @@ slot_launch_dma( slot_t * s, ulong c, uchar const * pub, uchar const * sig, uint
                             1, NULL, NULL, 0, NULL, s->strict ) )
     return FD_ED25519_AMD_ERR_DEVICE;
   HIPCHK( slot_out( s, s->m_err, s->d_err, c ) );
+  if( tag && slot_tags( s, c ) ) return FD_ED25519_AMD_ERR_DEVICE;
   HIPCHK( hipEventRecord( s->done, s->stream ) );
-  slot_in_flight( s, out, c );
+  slot_in_flight( s, out, tag, c );
   return FD_ED25519_AMD_OK;
 }
 
@@ -485,6 +546,13 @@ extern "C" int
 fd_ed25519_amd_verify_soa_registered( fd_ed25519_amd_t * e, ulong n, uchar const * pub, uchar const * sig,
                                       uint const * msg_off, uint const * msg_sz, uchar const * blob, ulong blob_sz,
                                       schar * err ) {
+  return fd_ed25519_amd_verify_soa_registered_tag( e, n, pub, sig, msg_off, msg_sz, blob, blob_sz, err, NULL );
+}
+
+extern "C" int
+fd_ed25519_amd_verify_soa_registered_tag( fd_ed25519_amd_t * e, ulong n, uchar const * pub, uchar const * sig,
+                                          uint const * msg_off, uint const * msg_sz, uchar const * blob, ulong blob_sz,
+                                          schar * err, ulong * tag ) {
   int rc = fd_amd_soa_args_check( e, n, pub, sig, msg_off, msg_sz, blob, blob_sz, err );
   if( rc ) return rc;
   if( !n ) return FD_ED25519_AMD_OK;
@@ -499,24 +567,28 @@ fd_ed25519_amd_verify_soa_registered( fd_ed25519_amd_t * e, ulong n, uchar const
        registered planes in place over PCIe, with no copy on either side --
        one chunk on a ring of one slot */
     return run_ring( e, 1, n, [&]( slot_t * s, ulong ) -> long {
+      if( tag ) { int rc = slot_alloc_tag( s, e->cap ); if( rc ) return rc; }
       /* the DSM kernel (strict mode: k_strict) writes the verdicts into the mapped h_err itself */
       if( fd_amd_launch_verify( (uint32_t)n, (uint8_t const *)d[0], (uint8_t const *)d[1], (uint32_t const *)d[2],
                                 (uint32_t const *)d[3], (uint8_t const *)d[4], s->d_err, s->d_ws, s->stream, 1, NULL,
                                 NULL, 0, (int8_t *)s->m_err, s->strict ) )
         return FD_ED25519_AMD_ERR_DEVICE;
+      if( tag && slot_tags( s, n ) ) return FD_ED25519_AMD_ERR_DEVICE;   /* k_tag_out after the DSM kernel, as slot_launch_packed */
       if( hipEventRecord( s->done, s->stream ) != hipSuccess ) return FD_ED25519_AMD_ERR_DEVICE;
-      slot_in_flight( s, err, n );
+      slot_in_flight( s, err, tag, n );
       return (long)n;
     } );
   return run_ring( e, e->nslot, n, [&]( slot_t * s, ulong i ) -> long {
+    if( tag ) { int rc = slot_alloc_tag( s, e->cap ); if( rc ) return rc; }
     soa_chunk_t ch = soa_chunk( e, n, i, msg_off, msg_sz, true );
+    ulong * const tg = tag ? tag + i : NULL;
     int rc;
     if( ch.win <= ch.bsz + ch.bsz/4UL + 4096UL )
       rc = slot_launch_dma( s, ch.c, pub + 32UL*i, sig + 64UL*i, msg_off + i, msg_sz + i, blob + ch.lo, ch.win,
-                            (uint)ch.lo, err + i );
+                            (uint)ch.lo, err + i, tg );
     else   /* scattered messages: gather them through the pinned staging */
       rc = slot_launch_packed( s, ch.c, soa_stage( s, ch, pub + 32UL*i, sig + 64UL*i, msg_off + i, msg_sz + i, blob, false ),
-                               err + i );
+                               err + i, tg );
     return rc ? rc : (long)ch.c;
   } );
 }
@@ -534,9 +606,9 @@ fd_amd_txn_slots1( uchar const * p, ulong sz ) {
 int
 fd_amd_txn_args_check( fd_ed25519_amd_t const * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
                        uint const * txn_sz, ulong payload_sz, schar const * txn_err, uint const * sig_base,
-                       schar const * sig_err ) {
+                       schar const * sig_err, ulong const * sig_tag ) {
   if( !e || (txn_cnt && (!payload || !txn_off || !txn_sz || !txn_err)) ) return FD_ED25519_AMD_ERR_INVAL;
-  if( sig_err && !sig_base ) return FD_ED25519_AMD_ERR_INVAL;
+  if( (sig_err || sig_tag) && !sig_base ) return FD_ED25519_AMD_ERR_INVAL;
   for( ulong t=0; t<txn_cnt; t++ ) {
     if( txn_sz[t] > FD_TXN_AMD_MTU || (ulong)txn_off[t] + txn_sz[t] > payload_sz || txn_sz[t] > e->blob_cap )
       return FD_ED25519_AMD_ERR_INVAL;
@@ -548,13 +620,21 @@ fd_amd_txn_args_check( fd_ed25519_amd_t const * e, ulong txn_cnt, uchar const * 
 extern "C" int
 fd_ed25519_amd_verify_txns( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
                             uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err ) {
-  int rc = fd_amd_txn_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err );
+  return fd_ed25519_amd_verify_txns_tag( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, NULL, NULL );
+}
+
+extern "C" int
+fd_ed25519_amd_verify_txns_tag( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
+                                uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                                ulong * txn_tag, ulong * sig_tag ) {
+  int rc = fd_amd_txn_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag );
   if( rc ) return rc;
   /* global signature numbering (the caller-visible sig_base) */
   if( sig_base ) fd_ed25519_amd_txn_slots( txn_cnt, payload, txn_off, txn_sz, sig_base );
   ulong gsig = 0;
   return run_ring( e, 2, txn_cnt, [&]( slot_t * s, ulong t ) -> long {
     int rc = slot_alloc_aux( s, e->cap );
+    if( !rc && (txn_tag || sig_tag) ) rc = slot_alloc_tag( s, e->cap );
     if( rc ) return rc;
     ulong c = 0, bsz = 0, ns = 0;
     while( t + c < txn_cnt && c < e->cap ) {
@@ -566,7 +646,8 @@ fd_ed25519_amd_verify_txns( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * p
       bsz += sz; ns += k2; c++;
     }
     s->h_tbase[c] = (uint32_t)ns;
-    rc = slot_launch_txn( s, c, ns, bsz, txn_err + t, sig_err ? sig_err + gsig : NULL );
+    rc = slot_launch_txn( s, c, ns, bsz, txn_err + t, sig_err ? sig_err + gsig : NULL, txn_tag ? txn_tag + t : NULL,
+                          sig_tag ? sig_tag + gsig : NULL );
     gsig += ns;
     return rc ? rc : (long)c;
   } );
@@ -728,6 +809,24 @@ fd_ed25519_amd_work_stats_dev( ulong n, void const * d_ws, uint * d_stats, void 
   uint8_t const * st = (uint8_t const *)d_ws + L.st;
   for( int k=0; k<3; k++ )
     HIPCHK( hipMemcpyAsync( d_stats + (ulong)k*n, st + 4UL*(ulong)k*L.N, 4UL*n, hipMemcpyDeviceToDevice, (hipStream_t)stream ) );
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" int
+fd_ed25519_amd_tags_dev( ulong n, void const * d_ws, ulong * d_tag, void * stream ) {
+  if( n > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !n ) return FD_ED25519_AMD_OK;
+  if( !d_ws || !d_tag || ((uintptr_t)d_tag & 7UL) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( fd_amd_launch_tag_out( d_tag, d_ws, n, (hipStream_t)stream ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" int
+fd_ed25519_amd_txn_tags_dev( ulong txn_cnt, uint const * d_tbase, void const * d_ws, ulong * d_txn_tag, void * stream ) {
+  if( txn_cnt > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !txn_cnt ) return FD_ED25519_AMD_OK;
+  if( !d_tbase || !d_ws || !d_txn_tag || ((uintptr_t)d_txn_tag & 7UL) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( fd_amd_launch_tag_gather( d_txn_tag, d_ws, (uint32_t)txn_cnt, d_tbase, (hipStream_t)stream ) ) return FD_ED25519_AMD_ERR_DEVICE;
   return FD_ED25519_AMD_OK;
 }
 

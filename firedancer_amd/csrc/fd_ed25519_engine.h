@@ -37,6 +37,15 @@ struct slot_t {
   ulong      t_n;
   schar *    s_out;      /* per-signature verdicts (optional) */
   ulong      s_n;
+  /* dedup tags (allocated by the first call that asks for them): one mapped
+     pinned buffer, h_tag[cap] for per-signature tags and h_ttag[cap] behind
+     it for per-transaction tags, both written in place by k_tag_out /
+     k_tag_gather; m_tag / m_ttag: their device addresses */
+  ulong * h_tag;  ulong * h_ttag;
+  void  * m_tag;  void  * m_ttag;
+  /* tags of the chunk in flight (NULL: not asked for): g_n from h_tag, tg_n from h_ttag */
+  ulong * g_out;  ulong g_n;
+  ulong * tg_out; ulong tg_n;
 };
 
 #define FD_AMD_SLOT_MAX (16)
@@ -67,12 +76,13 @@ fd_amd_mode_ok( int mode ) {
    anything launches, so an error never leaves a chunk in flight and the
    chunk loop always makes progress.  SoA: every message in bounds and small
    enough for one chunk.  Transactions: each in bounds and stageable in one
-   chunk (its bytes in blob_max, its signatures in batch_max). */
+   chunk (its bytes in blob_max, its signatures in batch_max); sig_base given
+   whenever a per-signature output (sig_err, sig_tag) is. */
 int fd_amd_soa_args_check( fd_ed25519_amd_t const * e, ulong n, uchar const * pub, uchar const * sig, uint const * msg_off,
                            uint const * msg_sz, uchar const * blob, ulong blob_sz, schar const * err );
 int fd_amd_txn_args_check( fd_ed25519_amd_t const * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
                            uint const * txn_sz, ulong payload_sz, schar const * txn_err, uint const * sig_base,
-                           schar const * sig_err );
+                           schar const * sig_err, ulong const * sig_tag );
 
 /* signature slots reserved for a payload (fd_txn_parse.c:79-82 rule) */
 ulong fd_amd_txn_slots1( uchar const * p, ulong sz );

@@ -336,6 +336,16 @@ fd_ed25519_sign( void * sig, void const * msg, unsigned long sz, void const * pu
   return sig;
 }
 
+/* The dedup tag's definition (include/fd_ed25519_amd.h, "Dedup tags"): the
+   little-endian u64 of the first 8 bytes of SHA-512( R || A || M ).  The
+   batch calls return the same value from the GPU's hash (k_prep). */
+unsigned long
+fd_ed25519_amd_tag( void const * msg, unsigned long sz, void const * sig, void const * public_key ) {
+  u8 h[64]; sha512 s; s.append( sig, 32 ); s.append( public_key, 32 ); if( sz ) s.append( msg, sz ); s.fini( h );
+  u64 t = 0; for( int j=7; j>=0; j-- ) t = (t << 8) | h[j];
+  return t;
+}
+
 /* Batch keygen + sign over the engine's SoA layout, nthread host threads:
    prv[n][32] -> pub[n][32], sig[n][64] over blob[msg_off[i] .. +msg_sz[i]). */
 int

@@ -155,4 +155,13 @@ int fd_amd_launch_rebase_off( uint32_t n, uint32_t * d_off, uint32_t const * d_s
 /* n bytes device -> mapped host memory by a kernel (no DMA engine). */
 int fd_amd_launch_copy_out( void * d_dst_mapped, void const * d_src, size_t n, hipStream_t stream );
 
+/* Dedup tags (k_tag_out): the n tags k_prep / k_front left in the tag plane
+   of workspace d_ws (the workspace of a verify launch of n signatures) ->
+   d_dst, u64 [n], 8-aligned device or mapped host memory.  Gather form:
+   d_dst[t] = the tag at slot d_tbase[t] for each of txn_cnt transactions, 0
+   for one without a slot; d_ws is the workspace of the verify launch over
+   d_tbase[txn_cnt] slots. */
+int fd_amd_launch_tag_out( void * d_dst, void const * d_ws, size_t n, hipStream_t stream );
+int fd_amd_launch_tag_gather( void * d_dst, void const * d_ws, uint32_t txn_cnt, uint32_t const * d_tbase, hipStream_t stream );
+
 #endif

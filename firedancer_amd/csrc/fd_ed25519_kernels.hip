@@ -28,7 +28,9 @@
  *   fd_ed25519_pool.h   k_ai, k_dsmp, k_fin (large batches)
  *   fd_ed25519_tile.h   k_tile_persist, k_tile_synth
  *   fd_ed25519_strict.h k_strict (strict mode's overlay, after the DSM stage)
- * This file keeps the launch code and the batch-size policy.
+ * This file keeps the launch code, the batch-size policy and the small
+ * kernels that move results out (k_copy_out: verdicts; k_tag_out /
+ * k_tag_gather: the dedup tags k_prep left in the workspace).
  */
 
 #include "fd_ed25519_dev.h"
@@ -101,6 +103,50 @@ fd_amd_launch_copy_out( void * d_dst, void const * d_src, size_t n, hipStream_t 
   size_t nb = ( (n >> 4) + 256u ) / 256u;
   if( nb > 4096u ) nb = 4096u;
   hipLaunchKernelGGL( k_copy_out, dim3((unsigned)nb), dim3(256), 0, stream, (u8 *)d_dst, (u8 const *)d_src, n );
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* Dedup tags: the tag plane k_prep / k_front left in the workspace -> dst,
+   device or mapped host memory.  16 B (two tags) per lane where dst is
+   16-aligned (the plane is 256-aligned), one tag per lane otherwise. */
+__global__ void __launch_bounds__(256)
+k_tag_out( u64 * __restrict__ dst, u64 const * __restrict__ tag, size_t n ) {
+  size_t i = (size_t)blockIdx.x * 256u + threadIdx.x, stride = (size_t)gridDim.x * 256u;
+  size_t nv = ((size_t)dst & 15u) ? 0 : (n >> 1);
+  for( size_t k = i; k < nv; k += stride ) ((ulong2 *)dst)[k] = ((ulong2 const *)tag)[k];
+  for( size_t k = (nv << 1) + i; k < n; k += stride ) dst[k] = tag[k];
+}
+
+/* The gather form: dst[t] = the tag of transaction t's first signature slot,
+   tag[tbase[t]]; 0 for a transaction without a slot.  A payload that failed
+   to parse either reserved no slot or had every slot skipped, and k_prep
+   writes tag 0 for a skipped slot; a payload that parsed has at least one
+   signature (fd_txn_parse.c:81).  The plane's offset depends on the slot
+   count the verify was launched with, tbase[txn_cnt]. */
+__global__ void __launch_bounds__(256)
+k_tag_gather( u64 * __restrict__ dst, u8 const * __restrict__ ws, u32 txn_cnt, u32 const * __restrict__ tbase ) {
+  u32 t = blockIdx.x * 256u + threadIdx.x;
+  if( t >= txn_cnt ) return;
+  u32 slots = tbase[txn_cnt], b = tbase[t], e = tbase[t+1u];
+  u64 const * tag = (u64 const *)(ws + ws_layout_const( slots ).tag);
+  dst[t] = ( b < e && b < slots ) ? tag[b] : 0UL;
+}
+
+int
+fd_amd_launch_tag_out( void * d_dst, void const * d_ws, size_t n, hipStream_t stream ) {
+  if( !n ) return 0;
+  size_t nb = ( (n >> 1) + 256u ) / 256u;
+  if( nb > 4096u ) nb = 4096u;
+  hipLaunchKernelGGL( k_tag_out, dim3((unsigned)nb), dim3(256), 0, stream, (u64 *)d_dst,
+                      (u64 const *)((u8 const *)d_ws + fd_amd_ws_layout( n ).tag), n );
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int
+fd_amd_launch_tag_gather( void * d_dst, void const * d_ws, uint32_t txn_cnt, uint32_t const * d_tbase, hipStream_t stream ) {
+  if( !txn_cnt ) return 0;
+  hipLaunchKernelGGL( k_tag_gather, dim3((txn_cnt + 255u)/256u), dim3(256), 0, stream, (u64 *)d_dst, (u8 const *)d_ws,
+                      txn_cnt, d_tbase );
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -139,6 +139,13 @@ extern "C" int
 fd_ed25519_amd_multi_verify_soa(fd_ed25519_amd_multi_t * m, ulong n, uchar const * pub, uchar const * sig,
                                  uint const * msg_off, uint const * msg_sz, uchar const * blob, ulong blob_sz,
                                  schar * err ) {
+  return fd_ed25519_amd_multi_verify_soa_tag( m, n, pub, sig, msg_off, msg_sz, blob, blob_sz, err, NULL );
+}
+
+extern "C" int
+fd_ed25519_amd_multi_verify_soa_tag( fd_ed25519_amd_multi_t * m, ulong n, uchar const * pub, uchar const * sig,
+                                     uint const * msg_off, uint const * msg_sz, uchar const * blob, ulong blob_sz,
+                                     schar * err, ulong * tag ) {
   /* validated once for the whole batch, so either every shard runs or none */
   if( !m || fd_amd_soa_args_check( m->eng[0], n, pub, sig, msg_off, msg_sz, blob, blob_sz, err ) ) return FD_ED25519_AMD_ERR_INVAL;
   if( !n ) return FD_ED25519_AMD_OK;
@@ -146,8 +153,8 @@ fd_ed25519_amd_multi_verify_soa(fd_ed25519_amd_multi_t * m, ulong n, uchar const
     ulong lo, hi;
     fd_ed25519_amd_shard_range( n, m->ndev, r, &lo, &hi );
     if( lo == hi ) return FD_ED25519_AMD_OK;
-    return fd_ed25519_amd_verify_soa( m->eng[r], hi - lo, pub + 32UL*lo, sig + 64UL*lo, msg_off + lo, msg_sz + lo,
-                                      blob, blob_sz, err + lo );
+    return fd_ed25519_amd_verify_soa_tag( m->eng[r], hi - lo, pub + 32UL*lo, sig + 64UL*lo, msg_off + lo, msg_sz + lo,
+                                          blob, blob_sz, err + lo, tag ? tag + lo : NULL );   /* the shard's tags at its offset */
   } );
 }
 
@@ -155,7 +162,16 @@ extern "C" int
 fd_ed25519_amd_multi_verify_txns( fd_ed25519_amd_multi_t * m, ulong txn_cnt, uchar const * payload, uint const * txn_off,
                                   uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base,
                                   schar * sig_err ) {
-  if( !m || fd_amd_txn_args_check( m->eng[0], txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err ) )
+  return fd_ed25519_amd_multi_verify_txns_tag( m, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err,
+                                               NULL, NULL );
+}
+
+extern "C" int
+fd_ed25519_amd_multi_verify_txns_tag( fd_ed25519_amd_multi_t * m, ulong txn_cnt, uchar const * payload, uint const * txn_off,
+                                      uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base,
+                                      schar * sig_err, ulong * txn_tag, ulong * sig_tag ) {
+  if( !m || fd_amd_txn_args_check( m->eng[0], txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err,
+                                   sig_tag ) )
     return FD_ED25519_AMD_ERR_INVAL;
   if( sig_base ) fd_ed25519_amd_txn_slots( txn_cnt, payload, txn_off, txn_sz, sig_base );   /* global numbering */
   if( !txn_cnt ) return FD_ED25519_AMD_OK;
@@ -164,7 +180,9 @@ fd_ed25519_amd_multi_verify_txns( fd_ed25519_amd_multi_t * m, ulong txn_cnt, uch
     fd_ed25519_amd_shard_range( txn_cnt, m->ndev, r, &lo, &hi );
     if( lo == hi ) return FD_ED25519_AMD_OK;
     std::vector<uint> base( sig_base ? hi - lo + 1UL : 0UL );
-    return fd_ed25519_amd_verify_txns( m->eng[r], hi - lo, payload, txn_off + lo, txn_sz + lo, payload_sz, txn_err + lo,
-                                       sig_base ? base.data() : NULL, sig_err ? sig_err + sig_base[lo] : NULL );
+    /* per-signature outputs in the whole batch's numbering: the shard's start at sig_base[lo] */
+    return fd_ed25519_amd_verify_txns_tag( m->eng[r], hi - lo, payload, txn_off + lo, txn_sz + lo, payload_sz, txn_err + lo,
+                                           sig_base ? base.data() : NULL, sig_err ? sig_err + sig_base[lo] : NULL,
+                                           txn_tag ? txn_tag + lo : NULL, sig_tag ? sig_tag + sig_base[lo] : NULL );
   } );
 }

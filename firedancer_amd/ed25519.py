@@ -149,7 +149,17 @@ def lib():
            "fd_ed25519_amd_dropin_set_device": ([i], i), "fd_ed25519_amd_dropin_device": ([], i),
            "fd_ed25519_amd_dropin_pick": ([ctypes.POINTER(i), i, i, ul], i),
            "fd_verify_amd_tile_level": ([i, i] + [ctypes.c_double] * 5, i),
-           "fd_verify_amd_tile_level_step": ([i, i, ul, ul, ctypes.POINTER(ul)], i)}
+           "fd_verify_amd_tile_level_step": ([i, i, ul, ul, ctypes.POINTER(ul)], i),
+           # dedup tags
+           "fd_ed25519_amd_tag": ([vp, ul, vp, vp], ul),
+           "fd_ed25519_amd_verify_batch_tag": ([vp, ul, c_void_pp, c_ulong_p, c_void_pp, c_void_pp, vp, vp], i),
+           "fd_ed25519_amd_verify_soa_tag": ([vp, ul, vp, vp, vp, vp, vp, ul, vp, vp], i),
+           "fd_ed25519_amd_verify_soa_registered_tag": ([vp, ul, vp, vp, vp, vp, vp, ul, vp, vp], i),
+           "fd_ed25519_amd_multi_verify_soa_tag": ([vp, ul, vp, vp, vp, vp, vp, ul, vp, vp], i),
+           "fd_ed25519_amd_verify_txns_tag": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp], i),
+           "fd_ed25519_amd_multi_verify_txns_tag": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp], i),
+           "fd_ed25519_amd_tags_dev": ([ul, vp, vp, vp], i),
+           "fd_ed25519_amd_txn_tags_dev": ([ul, vp, vp, vp, vp], i)}
     for name, (args, res) in opt.items():
         if hasattr(L, name) or not os.environ.get("FD_AMD_LIB"):
             f = getattr(L, name)
@@ -237,6 +247,18 @@ def sign_batch(prv, blob, msg_off, msg_sz, nthread=None):
     return pub, sig
 
 
+def tag(msg, sig, public_key):
+    """fd_ed25519_amd_tag: the dedup tag of (msg, sig, pub) -- the
+    little-endian u64 of the first 8 bytes of SHA-512(sig[0:32] || pub || msg),
+    on the host (no device).  The want_tags batch forms return it from the
+    GPU's hash, and 0 where the reference's s check rejects."""
+    m = bytes(msg)
+    s = bytes(sig)
+    p = bytes(public_key)
+    assert len(s) == 64 and len(p) == 32
+    return int(lib().fd_ed25519_amd_tag(m if m else None, len(m), s, p))
+
+
 # ---------------------------------------------------------------- batch engine
 
 class EngineError(RuntimeError):
@@ -290,7 +312,9 @@ class Engine:
         except Exception:
             pass
 
-    def verify_soa(self, pub, sig, msg_off, msg_sz, blob):
+    def verify_soa(self, pub, sig, msg_off, msg_sz, blob, want_tags=False):
+        """want_tags: returns (err, tag), tag uint64 (n,): the dedup tags
+        (fd_ed25519_amd_verify_soa_tag; see tag())."""
         pub = np.ascontiguousarray(pub, np.uint8)
         sig = np.ascontiguousarray(sig, np.uint8)
         off = np.ascontiguousarray(msg_off, np.uint32)
@@ -298,26 +322,39 @@ class Engine:
         blob = np.ascontiguousarray(blob, np.uint8)
         n = int(pub.shape[0])
         err = np.zeros(n, np.int8)
-        rc = lib().fd_ed25519_amd_verify_soa(self._h, n, _ptr(pub), _ptr(sig), _ptr(off), _ptr(sz),
-                                             _ptr(blob), int(blob.size), _ptr(err))
+        if want_tags:
+            tags = np.zeros(n, np.uint64)
+            rc = lib().fd_ed25519_amd_verify_soa_tag(self._h, n, _ptr(pub), _ptr(sig), _ptr(off), _ptr(sz),
+                                                     _ptr(blob), int(blob.size), _ptr(err), _ptr(tags))
+        else:
+            rc = lib().fd_ed25519_amd_verify_soa(self._h, n, _ptr(pub), _ptr(sig), _ptr(off), _ptr(sz),
+                                                 _ptr(blob), int(blob.size), _ptr(err))
         if rc:
             raise EngineError("fd_ed25519_amd_verify_soa rc=%d" % rc)
-        return err
+        return (err, tags) if want_tags else err
 
-    def verify_soa_registered(self, pub, sig, msg_off, msg_sz, blob, err=None):
+    def verify_soa_registered(self, pub, sig, msg_off, msg_sz, blob, err=None, want_tags=False):
         """fd_ed25519_amd_verify_soa_registered: every plane must lie in memory
-        registered with host_register (see RegisteredPlanes); no host copy."""
+        registered with host_register (see RegisteredPlanes); no host copy.
+        want_tags: returns (err, tag) as verify_soa (the outputs are plain
+        memory)."""
         n = int(pub.shape[0])
         if err is None:
             err = np.zeros(n, np.int8)
-        rc = lib().fd_ed25519_amd_verify_soa_registered(self._h, n, _ptr(pub), _ptr(sig), _ptr(msg_off), _ptr(msg_sz),
-                                                        _ptr(blob), int(blob.size), _ptr(err))
+        if want_tags:
+            tags = np.zeros(n, np.uint64)
+            rc = lib().fd_ed25519_amd_verify_soa_registered_tag(self._h, n, _ptr(pub), _ptr(sig), _ptr(msg_off),
+                                                                _ptr(msg_sz), _ptr(blob), int(blob.size), _ptr(err),
+                                                                _ptr(tags))
+        else:
+            rc = lib().fd_ed25519_amd_verify_soa_registered(self._h, n, _ptr(pub), _ptr(sig), _ptr(msg_off),
+                                                            _ptr(msg_sz), _ptr(blob), int(blob.size), _ptr(err))
         if rc:
             raise EngineError("fd_ed25519_amd_verify_soa_registered rc=%d" % rc)
-        return err
+        return (err, tags) if want_tags else err
 
-    def verify_batch(self, msgs, sigs, pubs):
-        """Pointer-array form: lists of bytes-like."""
+    def verify_batch(self, msgs, sigs, pubs, want_tags=False):
+        """Pointer-array form: lists of bytes-like.  want_tags: (err, tag)."""
         n = len(msgs)
         keep = [bytes(m) for m in msgs] + [bytes(s) for s in sigs] + [bytes(p) for p in pubs]
         bufs = [ctypes.create_string_buffer(b, max(len(b), 1)) for b in keep]
@@ -326,17 +363,24 @@ class Engine:
         pp = (ctypes.c_void_p * max(n, 1))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs[2 * n:]])
         sz = (ctypes.c_ulong * max(n, 1))(*[len(b) for b in keep[:n]])
         err = np.zeros(max(n, 1), np.int8)
-        rc = lib().fd_ed25519_amd_verify_batch(self._h, n, mp, sz, sp, pp, _ptr(err))
+        if want_tags:
+            tags = np.zeros(max(n, 1), np.uint64)
+            rc = lib().fd_ed25519_amd_verify_batch_tag(self._h, n, mp, sz, sp, pp, _ptr(err), _ptr(tags))
+        else:
+            rc = lib().fd_ed25519_amd_verify_batch(self._h, n, mp, sz, sp, pp, _ptr(err))
         if rc:
             raise EngineError("fd_ed25519_amd_verify_batch rc=%d" % rc)
-        return err[:n]
+        return (err[:n], tags[:n]) if want_tags else err[:n]
 
-    def verify_txns(self, payload, txn_off, txn_sz, want_sigs=False):
+    def verify_txns(self, payload, txn_off, txn_sz, want_sigs=False, want_tags=False):
         """Wire-format transaction batch (include/fd_txn_amd.h): parse on the
         GPU, verify every signature (multi-signer rule), one verdict per
         transaction in {0, -1, -2, -3, FD_TXN_AMD_ERR_PARSE}.  With
-        want_sigs, also returns (sig_base, sig_err)."""
-        return _verify_txns(lib().fd_ed25519_amd_verify_txns, self._h, payload, txn_off, txn_sz, want_sigs)
+        want_sigs, also returns (sig_base, sig_err); with want_tags the
+        tuple ends with (txn_tag, sig_tag): uint64 per transaction (its
+        first signature's dedup tag, 0 where it did not parse) and per
+        signature slot (the numbering of sig_err / txn_slots)."""
+        return _verify_txns("fd_ed25519_amd_verify_txns", self._h, payload, txn_off, txn_sz, want_sigs, want_tags)
 
 
 def txn_slots(payload, txn_off, txn_sz):
@@ -349,25 +393,35 @@ def txn_slots(payload, txn_off, txn_sz):
     return base, int(tot)
 
 
-def _verify_txns(fn, h, payload, txn_off, txn_sz, want_sigs):
+def _verify_txns(name, h, payload, txn_off, txn_sz, want_sigs, want_tags=False):
+    """name: fd_ed25519_amd_verify_txns or the multi form; want_tags calls its _tag form."""
     payload = np.ascontiguousarray(payload, np.uint8)
     off = np.ascontiguousarray(txn_off, np.uint32)
     sz = np.ascontiguousarray(txn_sz, np.uint32)
     n = int(off.size)
     terr = np.zeros(max(n, 1), np.int8)
     base = serr = None
-    if want_sigs:
-        # sig_err is sized by the engine's own slot rule (overlapping or
-        # repeated txn_off entries reserve slots more than once)
+    if want_sigs or want_tags:
+        # sig_err / sig_tag are sized by the engine's own slot rule (overlapping
+        # or repeated txn_off entries reserve slots more than once)
         base, tot = txn_slots(payload, off, sz)
+    if want_sigs:
         serr = np.zeros(max(tot, 1), np.int8)
-    rc = fn(h, n, _ptr(payload), _ptr(off), _ptr(sz), int(payload.size), _ptr(terr),
-            _ptr(base) if want_sigs else None, _ptr(serr) if want_sigs else None)
+    args = (h, n, _ptr(payload), _ptr(off), _ptr(sz), int(payload.size), _ptr(terr),
+            _ptr(base) if base is not None else None, _ptr(serr) if want_sigs else None)
+    if want_tags:
+        ttag, stag = np.zeros(max(n, 1), np.uint64), np.zeros(max(tot, 1), np.uint64)
+        rc = getattr(lib(), name + "_tag")(*args, _ptr(ttag), _ptr(stag))
+    else:
+        rc = getattr(lib(), name)(*args)
     if rc:
         raise EngineError("verify_txns rc=%d" % rc)
+    out = (terr[:n],)
     if want_sigs:
-        return terr[:n], base, serr[:int(base[-1])]
-    return terr[:n]
+        out += (base, serr[:int(base[-1])])
+    if want_tags:
+        out += (ttag[:n], stag[:int(base[-1])])
+    return out if len(out) > 1 else out[0]
 
 
 def shard_range(n, ndev, r):
@@ -411,7 +465,8 @@ class MultiEngine:
         except Exception:
             pass
 
-    def verify_soa(self, pub, sig, msg_off, msg_sz, blob):
+    def verify_soa(self, pub, sig, msg_off, msg_sz, blob, want_tags=False):
+        """want_tags: (err, tag) as Engine.verify_soa, every shard's tags at its offset."""
         pub = np.ascontiguousarray(pub, np.uint8)
         sig = np.ascontiguousarray(sig, np.uint8)
         off = np.ascontiguousarray(msg_off, np.uint32)
@@ -419,14 +474,19 @@ class MultiEngine:
         blob = np.ascontiguousarray(blob, np.uint8)
         n = int(pub.shape[0])
         err = np.zeros(max(n, 1), np.int8)
-        rc = lib().fd_ed25519_amd_multi_verify_soa(self._h, n, _ptr(pub), _ptr(sig), _ptr(off), _ptr(sz), _ptr(blob),
-                                                   int(blob.size), _ptr(err))
+        if want_tags:
+            tags = np.zeros(max(n, 1), np.uint64)
+            rc = lib().fd_ed25519_amd_multi_verify_soa_tag(self._h, n, _ptr(pub), _ptr(sig), _ptr(off), _ptr(sz),
+                                                           _ptr(blob), int(blob.size), _ptr(err), _ptr(tags))
+        else:
+            rc = lib().fd_ed25519_amd_multi_verify_soa(self._h, n, _ptr(pub), _ptr(sig), _ptr(off), _ptr(sz), _ptr(blob),
+                                                       int(blob.size), _ptr(err))
         if rc:
             raise EngineError("fd_ed25519_amd_multi_verify_soa rc=%d" % rc)
-        return err[:n]
+        return (err[:n], tags[:n]) if want_tags else err[:n]
 
-    def verify_txns(self, payload, txn_off, txn_sz, want_sigs=False):
-        return _verify_txns(lib().fd_ed25519_amd_multi_verify_txns, self._h, payload, txn_off, txn_sz, want_sigs)
+    def verify_txns(self, payload, txn_off, txn_sz, want_sigs=False, want_tags=False):
+        return _verify_txns("fd_ed25519_amd_multi_verify_txns", self._h, payload, txn_off, txn_sz, want_sigs, want_tags)
 
 
 class RegisteredPlanes:
@@ -520,6 +580,24 @@ def work_stats_dev(n, d_ws, d_stats, stream=0):
     rc = lib().fd_ed25519_amd_work_stats_dev(int(n), d_ws, d_stats, stream)
     if rc:
         raise EngineError("fd_ed25519_amd_work_stats_dev rc=%d" % rc)
+
+
+def tags_dev(n, d_ws, d_tag, stream=0):
+    """fd_ed25519_amd_tags_dev: the dedup tags (uint64 [n], device pointer)
+    of the last verify_dev / verify_txns_dev call on workspace d_ws, in
+    either mode.  Enqueued on `stream`, not synchronised."""
+    rc = lib().fd_ed25519_amd_tags_dev(int(n), d_ws, d_tag, stream)
+    if rc:
+        raise EngineError("fd_ed25519_amd_tags_dev rc=%d" % rc)
+
+
+def txn_tags_dev(txn_cnt, d_tbase, d_ws, d_txn_tag, stream=0):
+    """fd_ed25519_amd_txn_tags_dev: per transaction the dedup tag of its
+    first signature (0 where it did not parse), after verify_txns_dev on the
+    same workspace and d_tbase."""
+    rc = lib().fd_ed25519_amd_txn_tags_dev(int(txn_cnt), d_tbase, d_ws, d_txn_tag, stream)
+    if rc:
+        raise EngineError("fd_ed25519_amd_txn_tags_dev rc=%d" % rc)
 
 
 def debug_digits_dev(n, d_ws, d_dig, d_top, stream=0):

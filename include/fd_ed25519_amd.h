@@ -306,6 +306,81 @@ fd_ed25519_amd_multi_verify_soa( fd_ed25519_amd_multi_t * multi,
                                  ulong                    blob_sz,
                                  schar *                  err );
 
+/* Dedup tags.  The tile downstream of verify deduplicates on the mcache
+   `sig` field, which this project sets to a hash the verify computes anyway:
+
+     tag[i] = the little-endian u64 of bytes 0..7 of
+              SHA-512( sig[i][0:32] || pub[i] || msg[i] )
+
+   fd_ed25519_amd_tag is that definition as pure host code (no device; what
+   a unit test or a CPU-only caller computes).  Each *_tag batch call below
+   is the call it is named after plus `tag`, n entries of caller memory, and
+   returns for every signature the value the GPU already hashed:
+     - 0 where the engine does not hash: a signature the reference's s check
+       rejects (reference verdict FD_ED25519_ERR_SIG);
+     - the hash everywhere else: for verdicts 0, -2 and -3, and for an s the
+       reference's window accepts without a multiply (reference verdict 0);
+     - the same value in both verdict modes: an s-window signature is -1 in
+       FD_ED25519_AMD_MODE_STRICT and still carries its hash.
+   tag == NULL is exactly the untagged call (nothing more is launched or
+   copied); the untagged functions are these with tag == NULL.  Like err,
+   tag is written only during the call, and its contents are unspecified
+   when the call returns an error.  In-batch duplicates are not filtered:
+   dedup stays the caller's. */
+ulong
+fd_ed25519_amd_tag( void const * msg,
+                    ulong        sz,
+                    void const * sig,
+                    void const * public_key );
+
+int
+fd_ed25519_amd_verify_batch_tag( fd_ed25519_amd_t *   eng,
+                                 ulong                n,
+                                 void const * const * msg,
+                                 ulong const *        sz,
+                                 void const * const * sig,
+                                 void const * const * pub,
+                                 schar *              err,
+                                 ulong *              tag );
+
+int
+fd_ed25519_amd_verify_soa_tag( fd_ed25519_amd_t * eng,
+                               ulong              n,
+                               uchar const *      pub,
+                               uchar const *      sig,
+                               uint const *       msg_off,
+                               uint const *       msg_sz,
+                               uchar const *      blob,
+                               ulong              blob_sz,
+                               schar *            err,
+                               ulong *            tag );
+
+/* tag (like err) is plain caller memory: it need not be registered. */
+int
+fd_ed25519_amd_verify_soa_registered_tag( fd_ed25519_amd_t * eng,
+                                          ulong              n,
+                                          uchar const *      pub,
+                                          uchar const *      sig,
+                                          uint const *       msg_off,
+                                          uint const *       msg_sz,
+                                          uchar const *      blob,
+                                          ulong              blob_sz,
+                                          schar *            err,
+                                          ulong *            tag );
+
+/* Every shard writes its tags at its fd_ed25519_amd_shard_range offset. */
+int
+fd_ed25519_amd_multi_verify_soa_tag( fd_ed25519_amd_multi_t * multi,
+                                     ulong                    n,
+                                     uchar const *            pub,
+                                     uchar const *            sig,
+                                     uint const *             msg_off,
+                                     uint const *             msg_sz,
+                                     uchar const *            blob,
+                                     ulong                    blob_sz,
+                                     schar *                  err,
+                                     ulong *                  tag );
+
 /* Device-resident batch: every pointer is HIP device memory, already
    resident (the layout of fd_ed25519_amd_verify_soa).  Enqueues the
    verify kernels on `stream` (hipStream_t, NULL = default stream) and
@@ -378,6 +453,14 @@ fd_ed25519_amd_verify_dev_ev_mode( ulong         n,
    algorithmic multiply count.  Enqueued on `stream`. */
 int
 fd_ed25519_amd_work_stats_dev( ulong n, void const * d_ws, uint * d_stats, void * stream );
+
+/* The dedup tags (above) of the last device-resident call on the same
+   workspace, in either mode: d_tag[i], n entries of device memory (or
+   mapped host memory), 8-aligned.  Tags are not arguments of the
+   fd_ed25519_amd_verify_dev* calls: the verify leaves them in the
+   workspace and this reads them back.  Enqueued on `stream`, no sync. */
+int
+fd_ed25519_amd_tags_dev( ulong n, void const * d_ws, ulong * d_tag, void * stream );
 
 /* Debug: copy the signed sliding-window digits (u16 [n][256], low byte =
    digit of h = SHA-512(R||A||M) mod L, high byte = digit of s; recoding of

@@ -164,6 +164,42 @@ fd_ed25519_amd_multi_verify_txns( fd_ed25519_amd_multi_t * multi,
                                   uint *                   sig_base,
                                   schar *                  sig_err );
 
+/* The two calls above with the dedup tags (fd_ed25519_amd.h, "Dedup tags")
+   as two more optional outputs, either may be NULL:
+     txn_tag[t]  txn_cnt entries: the tag of transaction t's FIRST signature,
+                 which is what the verify tile publishes for it
+                 (fd_tango_amd.h); 0 for FD_TXN_AMD_ERR_PARSE.
+     sig_tag[s]  one per signature slot, in the numbering of sig_err (so
+                 sig_base is required with it, and the capacity is that of
+                 sig_err); 0 in the slots of a payload that failed to parse.
+   Both NULL is exactly the untagged call.  The multi-device form numbers
+   sig_tag over the whole batch, as it does sig_err. */
+int
+fd_ed25519_amd_verify_txns_tag( fd_ed25519_amd_t * eng,
+                                ulong              txn_cnt,
+                                uchar const *      payload,
+                                uint const *       txn_off,
+                                uint const *       txn_sz,
+                                ulong              payload_sz,
+                                schar *            txn_err,
+                                uint *             sig_base,
+                                schar *            sig_err,
+                                ulong *            txn_tag,
+                                ulong *            sig_tag );
+
+int
+fd_ed25519_amd_multi_verify_txns_tag( fd_ed25519_amd_multi_t * multi,
+                                      ulong                    txn_cnt,
+                                      uchar const *            payload,
+                                      uint const *             txn_off,
+                                      uint const *             txn_sz,
+                                      ulong                    payload_sz,
+                                      schar *                  txn_err,
+                                      uint *                   sig_base,
+                                      schar *                  sig_err,
+                                      ulong *                  txn_tag,
+                                      ulong *                  sig_tag );
+
 /* Device-resident form (inputs already in HBM, caller's stream, no sync).
    Signature slots follow the same rule as fd_ed25519_amd_verify_txns:
    d_tbase[t] (txn_cnt+1 entries, slot_cnt = d_tbase[txn_cnt]) is what
@@ -217,6 +253,20 @@ fd_ed25519_amd_verify_txns_dev_mode( ulong         txn_cnt,
                                      void *        d_ws,
                                      void *        stream,
                                      int           mode );
+
+/* Per-transaction dedup tags of the last fd_ed25519_amd_verify_txns_dev*
+   call on workspace d_ws, with the d_tbase it was given (txn_cnt+1 entries):
+   d_txn_tag[t] = the tag of transaction t's first signature, 0 for a
+   transaction that did not parse (txn_cnt entries, device or mapped host
+   memory, 8-aligned).  The per-signature tags of the same call are
+   fd_ed25519_amd_tags_dev( slot_cnt, d_ws, ... ).  Enqueued on `stream`,
+   no sync. */
+int
+fd_ed25519_amd_txn_tags_dev( ulong        txn_cnt,
+                             uint const * d_tbase,
+                             void const * d_ws,
+                             ulong *      d_txn_tag,
+                             void *       stream );
 
 /* Workload synthesis (config 4): txn_cnt well-formed legacy / v0
    transactions with nsig_lo..nsig_hi signers (account addresses = the
