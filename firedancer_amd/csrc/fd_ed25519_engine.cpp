@@ -855,6 +855,15 @@ fd_ed25519_amd_debug_points_dev( ulong n, void const * d_ws, int * d_A, int * d_
   return FD_ED25519_AMD_OK;
 }
 
+extern "C" int
+fd_ed25519_amd_debug_rprime_dev( ulong n, void const * d_ws, int kind, int * d_xyz, void * stream ) {
+  if( n > 0xFFFFFFFFUL || kind < FD_ED25519_AMD_DSM_DEFAULT || kind > FD_ED25519_AMD_DSM_K_DSMP ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !n ) return FD_ED25519_AMD_OK;
+  if( !d_ws || !d_xyz ) return FD_ED25519_AMD_ERR_INVAL;
+  if( fd_amd_launch_rprime( (uint32_t)n, d_ws, kind, d_xyz, (hipStream_t)stream ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  return FD_ED25519_AMD_OK;
+}
+
 /* ------------------------------------------------------------------ */
 /* drop-in reference API                                                */
 

@@ -35,7 +35,8 @@ int fd_amd_launch_verify( uint32_t n, uint8_t const * d_pub, uint8_t const * d_s
 #define FD_AMD_VERDICT_DEVICE (-128)
 /* dsm_mode: 0 = by batch size (fd_ed25519_amd_set_latency_batch_max,
    fd_ed25519_amd_set_small_batch_max), 1 = the throughput path (k_prep,
-   k_decomp, k_dsm), 2 = k_front + k_dsm4, 3 = k_front + k_dsm8. */
+   k_decomp, k_dsm), 2 = k_front + k_dsm4, 3 = k_front + k_dsm8, 4 = the
+   throughput path with the pooled DSM (k_ai, k_dsmp, k_fin). */
 
 /* Transaction front end (fd_txn_kernels.hip).
    k_txn_parse: one lane per transaction t = d_payload[d_toff[t] .. +d_tsz[t]).
@@ -148,6 +149,15 @@ int fd_amd_launch_digits_dense( uint32_t n, void const * d_ws, uint16_t * d_dig,
 
 /* 1 when a batch of n takes the latency kernels (k_front + k_dsm8/k_dsm4). */
 int fd_amd_uses_latency_path( uint32_t n, int dsm_mode );
+
+/* The DSM kernel fd_amd_launch_verify runs for a batch of n: 1 k_dsm,
+   2 k_dsm4, 3 k_dsm8, 4 k_dsmp (FD_ED25519_AMD_DSM_*). */
+int fd_amd_dsm_kind( uint32_t n, int dsm_mode );
+
+/* R' of the last call on workspace d_ws (debug): int32 [30][n], the X | Y | Z
+   limbs DSM kernel `kind` parked per signature (0 = the kernel the size rule
+   gives a batch of n now); defined only where the DSM ran. */
+int fd_amd_launch_rprime( uint32_t n, void const * d_ws, int kind, int32_t * d_xyz, hipStream_t stream );
 
 /* d_off[i] -= lo for every nonempty message (0 for empty ones). */
 int fd_amd_launch_rebase_off( uint32_t n, uint32_t * d_off, uint32_t const * d_sz, uint32_t lo, hipStream_t stream );

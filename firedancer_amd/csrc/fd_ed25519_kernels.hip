@@ -159,10 +159,16 @@ static volatile u32 g_dsm4_max = 16384u;
 static volatile u32 g_dsm8_max = 8192u;
 static volatile u32 g_pool_min = 1u << 19;   /* k_dsmp from 2^19 signatures (pooled A/B) */
 static volatile u64 g_pool_iter_cap = ~0UL;   /* debug: cap on k_dsmp's step loop (its hang guard) */
+static volatile u32 g_pool_waves_dbg = 0u;    /* debug: k_dsmp's grid whatever the batch size (0: the policy) */
 
 extern "C" void
 fd_ed25519_amd_debug_set_pool_iter_cap( unsigned long cap ) {
   g_pool_iter_cap = cap ? cap : ~0UL;
+}
+
+extern "C" void
+fd_ed25519_amd_debug_set_pool_waves( unsigned long w ) {
+  g_pool_waves_dbg = w > 0xFFFFFFFFUL ? 0xFFFFFFFFu : (u32)w;
 }
 
 extern "C" void
@@ -172,7 +178,9 @@ fd_ed25519_amd_set_pool_batch_min( unsigned long n ) {
 
 /* k_dsmp grid: one single-wave workgroup per resident wave slot (8 per CU:
    LDS-bound at FD_POOL_P slots, VGPR-bound at 2 waves per SIMD), fewer
-   when the batch would leave pools nearly empty */
+   when the batch would leave pools nearly empty.  The debug override
+   (fd_ed25519_amd_debug_set_pool_waves) replaces only the batch-size term:
+   tests use it to make few waves refill their slots at a small n. */
 static u32
 pool_waves( u32 n ) {
   static int cus = 0;
@@ -185,6 +193,8 @@ pool_waves( u32 n ) {
 #ifdef FD_AMD_DIAG
   if( char const * e = getenv( "FD_POOL_WAVES" ) ) { u32 v = (u32)atoi( e ); if( v ) wmax = v; }
 #endif
+  u32 const dbg = g_pool_waves_dbg;
+  if( dbg ) return dbg < wmax ? dbg : wmax;
   u32 want = (n + 63u) / 64u;
   return want < wmax ? (want ? want : 1u) : wmax;
 }
@@ -204,6 +214,46 @@ fd_amd_uses_latency_path( uint32_t n, int dsm_mode ) {
   return dsm_mode == 2 || dsm_mode == 3 || (dsm_mode == 0 && (n <= g_dsm4_max || n <= g_dsm8_max));
 }
 
+/* The DSM kernel a batch of n runs: the one place that applies the size
+   rule, for the launch below and for the R' read-back (which must decode the
+   parking layout of the kernel the launch chose). */
+int
+fd_amd_dsm_kind( uint32_t n, int dsm_mode ) {
+  if( fd_amd_uses_latency_path( n, dsm_mode ) )
+    return ( dsm_mode == 3 || (dsm_mode == 0 && n <= g_dsm8_max) ) ? STRICT_DSM8 : STRICT_DSM4;
+  return ( dsm_mode == 4 || (dsm_mode == 0 && n >= g_pool_min) ) ? STRICT_DSMP : STRICT_DSM;
+}
+
+/* debug: the R' = (X, Y, Z) each signature's DSM parked in its Ai slab, read
+   through the parking layout of DSM kernel `kind` (k_strict's own loaders)
+   -> int32 [30][n], X | Y | Z limbs.  Rows of signatures whose DSM did not
+   run are whatever the slab holds. */
+__global__ void __launch_bounds__(64)
+k_rprime( u32 n, u8 const * __restrict__ ws, ws_layout_t L, int kind, i32 * __restrict__ out ) {
+  u32 const i = blockIdx.x * 64u + threadIdx.x;
+  if( i >= n ) return;
+  i32 const * Ail = (i32 const *)(ws + L.Ai) + (size_t)i*384u;
+  fe X, Y, Z;
+  switch( kind ) {
+  case STRICT_DSM:  dsm_load_parked ( X, Y, Z, Ail ); break;
+  case STRICT_DSM4: dsm4_load_parked( X, Y, Z, Ail ); break;
+  case STRICT_DSM8: dsm8_load_parked( X, Y, Z, Ail ); break;
+  default:          pool_load_parked( X, Y, Z, Ail, ((int const *)(ws + L.top))[i] ); break;
+  }
+  _Pragma("unroll") for( int k=0; k<10; k++ ) {
+    out[(size_t)k*n + i] = X.v[k]; out[(size_t)(10+k)*n + i] = Y.v[k]; out[(size_t)(20+k)*n + i] = Z.v[k];
+  }
+}
+
+int
+fd_amd_launch_rprime( uint32_t n, void const * d_ws, int kind, int32_t * d_xyz, hipStream_t stream ) {
+  if( !n ) return 0;
+  if( !kind ) kind = fd_amd_dsm_kind( n, 0 );
+  if( kind < STRICT_DSM || kind > STRICT_DSMP ) return -1;
+  hipLaunchKernelGGL( k_rprime, dim3((n + 63u)/64u), dim3(64), 0, stream, n, (u8 const *)d_ws, fd_amd_ws_layout( n ), kind, d_xyz );
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int
 fd_amd_launch_verify( u32 n, u8 const * d_pub, u8 const * d_sig, u32 const * d_off, u32 const * d_sz,
                       u8 const * d_blob, i8 * d_err, void * d_ws, hipStream_t stream, int want_stats,
@@ -212,20 +262,17 @@ fd_amd_launch_verify( u32 n, u8 const * d_pub, u8 const * d_sig, u32 const * d_o
   ws_layout_t L = fd_amd_ws_layout( n );
   u8 * ws = (u8 *)d_ws;
   u32 nb = (n + 63u) / 64u;
-  bool small = fd_amd_uses_latency_path( n, dsm_mode );
-  bool eight = dsm_mode == 3 || (dsm_mode == 0 && n <= g_dsm8_max);
+  int const kind = fd_amd_dsm_kind( n, dsm_mode );
+  bool const small = kind == STRICT_DSM4 || kind == STRICT_DSM8, eight = kind == STRICT_DSM8, pooled = kind == STRICT_DSMP;
   /* strict mode: k_strict writes the verdicts that go to d_out, the DSM kernel none */
   i8 * const dsm_out = strict ? NULL : d_out;
-  int kind;
   if( ev ) (void)hipEventRecord( ev[0], stream );
   if( small ) {   /* latency path: one front launch (hash || decompress), then k_dsm8 or k_dsm4 */
     hipLaunchKernelGGL( k_front, dim3(3u*nb), dim3(64), 0, stream, n, nb, d_pub, d_sig, d_off, d_sz, d_blob, d_err, ws, L, d_skip );
     if( ev ) { (void)hipEventRecord( ev[1], stream ); (void)hipEventRecord( ev[2], stream ); }
     if( eight ) hipLaunchKernelGGL( k_dsm8, dim3((n + 7u)/8u), dim3(64), 0, stream, n, d_err, ws, L, want_stats, dsm_out );
     else        hipLaunchKernelGGL( k_dsm4, dim3((n + 15u)/16u), dim3(64), 0, stream, n, d_err, ws, L, want_stats, dsm_out );
-    kind = eight ? STRICT_DSM8 : STRICT_DSM4;
   } else {
-    bool pooled = dsm_mode == 4 || (dsm_mode == 0 && n >= g_pool_min);
     hipLaunchKernelGGL( k_prep,   dim3(nb),    dim3(64), 0, stream, n, d_pub, d_sig, d_off, d_sz, d_blob, d_err, ws, L, d_skip );
     if( ev ) (void)hipEventRecord( ev[1], stream );
     hipLaunchKernelGGL( k_decomp, dim3(2u*nb), dim3(64), 0, stream, n, d_pub, d_sig, d_err, ws, L );
@@ -237,7 +284,6 @@ fd_amd_launch_verify( u32 n, u8 const * d_pub, u8 const * d_sig, u32 const * d_o
     } else {
       hipLaunchKernelGGL( k_dsm,  dim3(nb),    dim3(64), 0, stream, n, d_err, ws, L, want_stats );
     }
-    kind = pooled ? STRICT_DSMP : STRICT_DSM;
   }
   if( strict )   /* the overlay: re-decide every verdict (fd_ed25519_strict.h); d_out as the DSM kernel would have used it */
     hipLaunchKernelGGL( k_strict, dim3(nb), dim3(64), 0, stream, n, d_pub, d_sig, d_err, (u8 const *)ws, L, d_skip, kind,

@@ -159,7 +159,10 @@ def lib():
            "fd_ed25519_amd_verify_txns_tag": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp], i),
            "fd_ed25519_amd_multi_verify_txns_tag": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp], i),
            "fd_ed25519_amd_tags_dev": ([ul, vp, vp, vp], i),
-           "fd_ed25519_amd_txn_tags_dev": ([ul, vp, vp, vp, vp], i)}
+           "fd_ed25519_amd_txn_tags_dev": ([ul, vp, vp, vp, vp], i),
+           # debug: k_dsmp's grid, the parked R'
+           "fd_ed25519_amd_debug_set_pool_waves": ([ul], None),
+           "fd_ed25519_amd_debug_rprime_dev": ([ul, vp, i, vp, vp], i)}
     for name, (args, res) in opt.items():
         if hasattr(L, name) or not os.environ.get("FD_AMD_LIB"):
             f = getattr(L, name)
@@ -666,6 +669,26 @@ def device_numa_node(device):
 def debug_set_pool_iter_cap(cap):
     """Debug: cap k_dsmp's step guard at `cap` steps per wave (0 restores it)."""
     lib().fd_ed25519_amd_debug_set_pool_iter_cap(int(cap))
+
+
+def debug_set_pool_waves(w):
+    """Debug: launch k_dsmp with min(w, 8 per CU) waves whatever the batch size
+    (0 restores the policy min(ceil(n / 64), 8 per CU))."""
+    lib().fd_ed25519_amd_debug_set_pool_waves(int(w))
+
+
+DSM_KINDS = {"default": 0, "k_dsm": 1, "k_dsm4": 2, "k_dsm8": 3, "k_dsmp": 4}   # FD_ED25519_AMD_DSM_*
+
+
+def debug_rprime_dev(n, d_ws, kind, d_xyz, stream=0):
+    """The R' = [s]B - [h]A that the last device-resident call parked in
+    workspace d_ws: d_xyz int32 [30][n] (X | Y | Z limbs), read through the
+    parking layout of DSM kernel `kind` (a select_dsm_kernel name; 'default'
+    resolves by n under the thresholds set now, as the launch does).  A row is
+    defined only where the multiply ran."""
+    rc = lib().fd_ed25519_amd_debug_rprime_dev(int(n), d_ws, DSM_KINDS[kind], d_xyz, stream)
+    if rc:
+        raise EngineError("fd_ed25519_amd_debug_rprime_dev rc=%d" % rc)
 
 
 def select_dsm_kernel(name):

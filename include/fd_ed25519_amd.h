@@ -537,6 +537,36 @@ fd_ed25519_amd_set_pool_batch_min( ulong n );
 void
 fd_ed25519_amd_debug_set_pool_iter_cap( ulong cap );
 
+/* Debug: k_dsmp's grid.  By default a batch of n launches min( ceil(n/64),
+   8 per CU ) waves, each holding a pool of 112 signatures, so below
+   64 * 8 * CUs signatures no wave ever refills a slot a finished signature
+   freed.  w > 0 launches min( w, 8 per CU ) waves whatever n is (tests: one
+   or a few waves working through a small batch, every slot reused); 0
+   restores the policy.  Launch code only; verdicts do not depend on it.
+   Process-wide. */
+void
+fd_ed25519_amd_debug_set_pool_waves( ulong w );
+
+/* Debug: the double-scalar multiply's output R' = [s]B - [h]A that the last
+   device-resident call left parked in workspace `d_ws`, read through the
+   parking layout of DSM kernel `kind` (the loaders strict mode uses): d_xyz
+   int [30][n], the limbs of X | Y | Z (a projective point; reference:
+   avx/fd_ed25519_ge.c:408-527, the operands of the compare at
+   user.c:417-425).  kind names the kernel that ran: FD_ED25519_AMD_DSM_K_*,
+   or FD_ED25519_AMD_DSM_DEFAULT for the one the batch-size rule above gives
+   n signatures under the thresholds set now (the same function chooses the
+   kernel at launch).  A row is defined only for a signature whose multiply
+   ran: one that passed the s check (not -1, not the s window's early 0) and
+   whose A and R decoded (not -2); the other rows hold unspecified values.
+   Not defined after the step guard tripped.  Enqueued on `stream`. */
+#define FD_ED25519_AMD_DSM_DEFAULT (0)
+#define FD_ED25519_AMD_DSM_K_DSM   (1)
+#define FD_ED25519_AMD_DSM_K_DSM4  (2)
+#define FD_ED25519_AMD_DSM_K_DSM8  (3)
+#define FD_ED25519_AMD_DSM_K_DSMP  (4)
+int
+fd_ed25519_amd_debug_rprime_dev( ulong n, void const * d_ws, int kind, int * d_xyz, void * stream );
+
 /* Library version / build string. */
 char const *
 fd_ed25519_amd_version( void );

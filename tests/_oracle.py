@@ -33,6 +33,10 @@ def oracle():
         L.oracle_ed25519_verify.restype = ctypes.c_int
         L.oracle_ed25519_verify_batch.argtypes = [ctypes.c_uint64, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int]
         L.oracle_ed25519_verify_batch.restype = ctypes.c_int
+        L.oracle_ed25519_verify_rprime.argtypes = [vp, ctypes.c_size_t, vp, vp, vp, vp]
+        L.oracle_ed25519_verify_rprime.restype = ctypes.c_int
+        L.oracle_ed25519_rprime_batch.argtypes = [ctypes.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int]
+        L.oracle_ed25519_rprime_batch.restype = ctypes.c_int
         L.oracle_sha512.argtypes = [vp, ctypes.c_size_t, vp]
         L.oracle_sha512.restype = None
         L.oracle_sc_reduce.argtypes = [vp, vp]
@@ -182,6 +186,32 @@ def verify_batch(batch, nthread=None, stats=False):
         _p(np.ascontiguousarray(batch.msg_off)), _p(np.ascontiguousarray(batch.msg_sz)),
         _p(np.ascontiguousarray(batch.blob)), _p(err), _p(st) if stats else None, nthread)
     return (err, st) if stats else err
+
+
+def rprime(msg, sig, pub):
+    """(verdict, ran, xyz): oracle.verify's verdict, whether the double-scalar
+    multiply ran (False: s >= L, the s window's early 0, an undecodable
+    point), and then its output R' = [s]B - [h]A as int32 (3, 10): the limbs
+    of X, Y, Z (zeros when it did not run)."""
+    m = bytes(msg)
+    ran = ctypes.c_int(0)
+    xyz = np.zeros(30, np.int32)
+    rc = oracle().oracle_ed25519_verify_rprime(m if m else None, len(m), bytes(sig), bytes(pub), ctypes.byref(ran), _p(xyz))
+    return rc, bool(ran.value), xyz.reshape(3, 10)
+
+
+def rprime_batch(batch, nthread=None):
+    """rprime over a batch, threaded like verify_batch: (err int8 [n], ran
+    bool [n], xyz int32 [n][30])."""
+    n = len(batch)
+    err, ran, xyz = np.zeros(n, np.int8), np.zeros(n, np.uint8), np.zeros((n, 30), np.int32)
+    if nthread is None:
+        nthread = min(16, os.cpu_count() or 1)
+    oracle().oracle_ed25519_rprime_batch(
+        n, _p(np.ascontiguousarray(batch.pub)), _p(np.ascontiguousarray(batch.sig)),
+        _p(np.ascontiguousarray(batch.msg_off)), _p(np.ascontiguousarray(batch.msg_sz)),
+        _p(np.ascontiguousarray(batch.blob)), _p(err), _p(ran), _p(xyz), nthread)
+    return err, ran.astype(bool), xyz
 
 
 def sha512(data):

@@ -59,6 +59,29 @@ def test_reference_codes_and_strerror():
         assert re.search(r"#define %s\s+\(\s*%d\)" % (name, val), hdr), name
 
 
+def test_debug_rprime_and_pool_waves_arguments():
+    """The debug entry points exist and refuse bad arguments before anything
+    launches: an unknown kernel kind, NULL buffers, n past 2^32; an empty
+    batch is OK.  The wave-count knob takes any value and 0 (no device work)."""
+    from firedancer_amd import ed25519
+    L = ed25519.lib()
+    names = declared_functions()
+    assert "fd_ed25519_amd_debug_rprime_dev" in names and "fd_ed25519_amd_debug_set_pool_waves" in names
+    hdr = open(os.path.join(ROOT, "include", "fd_ed25519_amd.h")).read()
+    for name, val in ed25519.DSM_KINDS.items():
+        macro = "FD_ED25519_AMD_DSM_" + ("DEFAULT" if name == "default" else name.upper())
+        assert re.search(r"#define %s\s+\(%d\)" % (macro, val), hdr), macro
+    f = L.fd_ed25519_amd_debug_rprime_dev
+    buf = ctypes.create_string_buffer(256)
+    p = ctypes.addressof(buf)
+    assert f(0, None, 0, None, None) == 0
+    assert f(64, None, 0, p, None) == -10 and f(64, p, 0, None, None) == -10
+    assert f(64, p, 5, p, None) == -10 and f(64, p, -1, p, None) == -10
+    assert f(1 << 32, p, 1, p, None) == -10
+    ed25519.debug_set_pool_waves(3)
+    ed25519.debug_set_pool_waves(0)
+
+
 def test_workspace_footprint_monotone():
     from firedancer_amd import ed25519
     a, b, c = (ed25519.workspace_footprint(n) for n in (1, 64, 1 << 20))
