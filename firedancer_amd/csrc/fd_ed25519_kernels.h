@@ -41,7 +41,9 @@ int fd_amd_launch_verify( uint32_t n, uint8_t const * d_pub, uint8_t const * d_s
 /* Transaction front end (fd_txn_kernels.hip).
    k_txn_parse: one lane per transaction t = d_payload[d_toff[t] .. +d_tsz[t]).
      d_fp[t] = fd_txn_parse return value; d_out (optional) + t*out_stride gets
-     the fd_txn_t descriptor.  When d_tbase != NULL it also lays out the
+     the fd_txn_t descriptor: the header, and every instruction and
+     lookup-table record that ends within out_stride (all of them when
+     d_fp[t] <= out_stride).  When d_tbase != NULL it also lays out the
      transaction's signatures for the verify kernels at slots
      [d_tbase[t], d_tbase[t+1]): pub/sig copied from the payload, msg_off/msg_sz
      pointing at the shared message inside d_payload, skip = 0; a payload that

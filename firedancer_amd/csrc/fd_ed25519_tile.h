@@ -169,7 +169,7 @@ tile_txn_layout( u32 l, u32 k, u32 e_sz, u32 e_k, u8 const * __restrict__ mir, u
   u32 * info = lds + 64;       /* [64][5]: sig_off, acct_off, msg_off (~0: not parsed), frag size, first slot */
   if( l < k ) {
     u32 nsig = 0u, sig_off = 0u, acct_off = 0u, msg_off = 0u;
-    u32 const fp = fd_txn_dev::txn_parse( mir + (size_t)l * TILE_FRAME, e_sz, (u8 *)0, &nsig, &sig_off, &acct_off, &msg_off );
+    u32 const fp = fd_txn_dev::txn_parse( mir + (size_t)l * TILE_FRAME, e_sz, (u8 *)0, 0u, &nsig, &sig_off, &acct_off, &msg_off );
     u32 const ok = fp != 0u && nsig == kk && base + kk <= 64u;   /* the host packs <= 64 slots per chunk */
     for( u32 i=0u; i<kk && base + i < 64u; i++ ) own[base + i] = l;
     u32 * in = info + 5u*l;

@@ -58,11 +58,18 @@ struct cur_t {
 __device__ __forceinline__ void st16( u8 * o, u32 off, u32 v ) { *(u16 *)(o + off) = (u16)v; }
 
 /* The parse proper.  Writes descriptor fields to o (may be NULL: validate
-   only; instruction records are then kept in a tiny local ring for the
-   final index checks, re-read from the payload).  Returns the footprint or
-   0, and the three offsets the verify layout needs. */
+   only; the final index checks re-read the instructions from the payload
+   either way).  o has room for ocap >= TX_HDR bytes: an instruction or
+   lookup-table record is stored only if it ends at or before ocap, because
+   the records are stored during the walk, before the payload is known to
+   be acceptable, and a payload of up to 65535 B can hold 21789 instructions
+   (footprint 217910).  Returns the reference's footprint or 0 whatever
+   ocap is, so footprint > ocap tells the caller that o holds the header
+   and only the records that fit; and the three offsets the verify layout
+   needs. */
 __device__ inline u32
-txn_parse( u8 const * payload, u32 sz, u8 * o, u32 * nsig_out, u32 * sigoff_out, u32 * acctoff_out, u32 * msgoff_out ) {
+txn_parse( u8 const * payload, u32 sz, u8 * o, u32 ocap, u32 * nsig_out, u32 * sigoff_out, u32 * acctoff_out,
+           u32 * msgoff_out ) {
   cur_t c = { payload, sz, 0u };
   if( sz > 0xffffu ) return 0u;                                        /* :73 */
   if( !c.room( 1u ) ) return 0u;                                       /* :79 */
@@ -111,7 +118,7 @@ txn_parse( u8 const * payload, u32 sz, u8 * o, u32 * nsig_out, u32 * sigoff_out,
     if( !c.cu16( &ndata ) ) return 0u;                                 /* :139 */
     if( !c.room( ndata ) ) return 0u;                                  /* :140 */
     u32 d_off = c.at; c.at += ndata;
-    if( o ) {
+    if( o && (u32)TX_HDR + IX_SZ*(j+1u) <= ocap ) {
       u8 * ix = o + TX_HDR + IX_SZ*j;
       ix[0] = (u8)prog; ix[1] = 0u;
       st16( ix, 2, nacc ); st16( ix, 4, ndata ); st16( ix, 6, a_off ); st16( ix, 8, d_off );
@@ -135,7 +142,7 @@ txn_parse( u8 const * payload, u32 sz, u8 * o, u32 * nsig_out, u32 * sigoff_out,
       u32 r_off = c.at; c.at += nr;
       if( nw > TXN_ACCT_ADDR_MAX - nacct ) return 0u;                  /* :175 */
       if( nr > TXN_ACCT_ADDR_MAX - nacct ) return 0u;                  /* :176 */
-      if( o ) {
+      if( o && (u32)TX_HDR + IX_SZ*ninstr + LUT_SZ*(j+1u) <= ocap ) {
         u8 * l = o + TX_HDR + IX_SZ*ninstr + LUT_SZ*j;
         st16( l, 0, addr ); l[2] = (u8)nw; l[3] = (u8)nr; st16( l, 4, w_off ); st16( l, 6, r_off );
       }

@@ -48,7 +48,9 @@ k_txn_parse( u32 txn_cnt, u8 const * __restrict__ payload, u32 const * __restric
   u8 const * p = payload + toff[t];
   u32 sz = tsz[t];
   u32 nsig = 0u, sig_off = 0u, acct_off = 0u, msg_off = 0u;
-  u32 fp = txn_parse( p, sz, out ? out + (size_t)t*out_stride : (u8 *)0, &nsig, &sig_off, &acct_off, &msg_off );
+  /* no footprint reaches 2^32 - 1, so a wider stride bounds nothing */
+  u32 cap = out_stride < 0xffffffffUL ? (u32)out_stride : 0xffffffffu;
+  u32 fp = txn_parse( p, sz, out ? out + (size_t)t*out_stride : (u8 *)0, cap, &nsig, &sig_off, &acct_off, &msg_off );
   if( fp_out ) fp_out[t] = fp;
   if( !tbase ) return;
   u32 b = tbase[t], e = tbase[t+1u];

@@ -113,7 +113,34 @@ fd_txn_get_address_tables( fd_txn_t * txn ) {
    +d_txn_sz[t]).  Writes d_footprint[t] = what fd_txn_parse returns (0 on
    failure, else fd_txn_footprint) and, when d_out != NULL, the fd_txn_t
    descriptor to d_out + t*out_stride (out_stride >= FD_TXN_MAX_SZ, multiple
-   of 2).  Enqueued on `stream`; returns 0 or FD_ED25519_AMD_ERR_*. */
+   of 2).  Enqueued on `stream`; returns 0 or FD_ED25519_AMD_ERR_*.
+
+   Payloads are not capped at the MTU here: like the reference's
+   fd_txn_parse, the parser accepts any well-formed payload of up to 65535
+   bytes.  FD_TXN_MAX_SZ = 3570 is the largest footprint of a payload of at
+   most FD_TXN_AMD_MTU = 1232 bytes only (fd_txn.h:88-92).  The worst case
+   is a legacy payload with one signature, two account addresses (the fee
+   payer and a program: an instruction's program index must be >= 1) and
+   nothing but empty 3-byte instructions: 1 signature count + 64 signature
+   + 3 header + 1 account count + 64 accounts + 32 blockhash + 2 instruction
+   count = 167 bytes leave (1232 - 167) / 3 = 355 instructions, and
+   sizeof(fd_txn_t) + 355*sizeof(fd_txn_instr_t) = 20 + 10*355 = 3570.  The
+   same shape at 65535 bytes (the count then takes 3 bytes: 168) holds
+   (65535 - 168) / 3 = 21789 instructions, footprint 20 + 10*21789 = 217910;
+   no payload's footprint exceeds FD_TXN_AMD_FOOTPRINT_MAX.
+
+   Nothing is ever written outside [d_out + t*out_stride, + out_stride):
+   the 20-byte header always fits, and an instruction or lookup-table record
+   is stored only if it ends at or before out_stride.  d_footprint[t] stays
+   the reference's value, so d_footprint[t] > out_stride says that the
+   descriptor of t holds the header and the leading records that fit, not
+   the whole of it; a caller that wants every descriptor whole for payloads
+   above the MTU uses out_stride = FD_TXN_AMD_FOOTPRINT_MAX.  The records
+   are stored while the payload is walked, so the row of a rejected payload
+   (d_footprint[t] == 0) holds unspecified bytes, within the same bound. */
+#define FD_TXN_AMD_PAYLOAD_MAX   (65535UL)   /* fd_txn_parse.c:73 */
+#define FD_TXN_AMD_FOOTPRINT_MAX (20UL + 10UL*(FD_TXN_AMD_PAYLOAD_MAX/3UL) + 8UL*254UL)   /* 220502: every
+                                    instruction takes >= 3 payload bytes, at most 254 lookup tables */
 int
 fd_txn_amd_parse_dev( ulong         txn_cnt,
                       uchar const * d_payload,

@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <stddef.h>
+#include <stdlib.h>
 #include <pthread.h>
 
 typedef unsigned char  uchar;
@@ -30,6 +31,16 @@ typedef unsigned int   uint;
 typedef signed char    schar;
 
 #include "../include/fd_txn_amd.h"
+
+/* Capacity of every descriptor buffer the checker parses into.  The parser
+   accepts payloads of up to 65535 B (fd_txn_parse.c:73) and stores records
+   while it walks, so FD_TXN_MAX_SZ (the bound for payloads of at most
+   1232 B) is not enough: every instruction takes at least 3 payload bytes
+   and there are at most 254 lookup tables, so no walk stores past
+   20 + 10*(65535/3) + 8*254 = 220502 bytes. */
+#define ORACLE_TXN_DESC_MAX FD_TXN_AMD_FOOTPRINT_MAX
+
+ulong oracle_txn_desc_max( void ) { return ORACLE_TXN_DESC_MAX; }
 
 /* compact-u16 length (fd_compact_u16.h:69-87): 1..3 on success, 0 if the
    encoding is truncated, non-minimal or exceeds 16 bits. */
@@ -215,7 +226,9 @@ parse( uchar const * payload, ulong sz, void * out_buf, ulong * fail_line ) {
 # undef NEED
 }
 
-/* Same contract as fd_txn_parse (fd_txn.h:377-389). */
+/* Same contract as fd_txn_parse (fd_txn.h:377-389), but for the room
+   out_buf needs: oracle_txn_desc_max() bytes, unless every payload is at
+   most 1232 B (then FD_TXN_MAX_SZ). */
 ulong
 oracle_txn_parse( uchar const *             payload,
                   ulong                     payload_sz,
@@ -233,9 +246,11 @@ oracle_txn_parse( uchar const *             payload,
 /* Line of the reference check that rejects the payload (0 if it parses). */
 ulong
 oracle_txn_parse_fail_line( uchar const * payload, ulong payload_sz ) {
-  static __thread uchar buf[ FD_TXN_MAX_SZ ] __attribute__((aligned(8)));
+  void * buf = malloc( ORACLE_TXN_DESC_MAX );
   ulong line = 0UL;
+  if( !buf ) return ~0UL;
   (void)parse( payload, payload_sz, buf, &line );
+  free( buf );
   return line;
 }
 
@@ -261,12 +276,14 @@ typedef struct {
   ulong lo, hi;
   uchar const * payload; uint const * off; uint const * sz;
   schar * txn_err; uint const * base; schar * sig_err;
+  int fail;
 } txn_job_t;
 
 static void *
 txn_worker( void * arg ) {
   txn_job_t * j = (txn_job_t *)arg;
-  uchar buf[ FD_TXN_MAX_SZ ] __attribute__((aligned(8)));
+  uchar * buf = (uchar *)malloc( ORACLE_TXN_DESC_MAX );   /* per thread, off the stack */
+  if( !buf ) { j->fail = 1; return NULL; }
   for( ulong t=j->lo; t<j->hi; t++ ) {
     uchar const * p = j->payload + j->off[ t ];
     ulong line;
@@ -286,10 +303,12 @@ txn_worker( void * arg ) {
     }
     j->txn_err[ t ] = (schar)first;
   }
+  free( buf );
   return NULL;
 }
 
-/* sig_base is always filled (needs txn_cnt+1 entries); sig_err optional. */
+/* sig_base is always filled (needs txn_cnt+1 entries); sig_err optional.
+   Returns 0, or -1 if a worker could not allocate its descriptor buffer. */
 int
 oracle_txn_verify_batch( ulong txn_cnt, uchar const * payload, uint const * txn_off, uint const * txn_sz,
                          schar * txn_err, uint * sig_base, schar * sig_err, int nthread ) {
@@ -304,9 +323,10 @@ oracle_txn_verify_batch( ulong txn_cnt, uchar const * payload, uint const * txn_
   pthread_t th[ 64 ]; txn_job_t jb[ 64 ];
   for( int k=0; k<nthread; k++ ) {
     jb[ k ] = (txn_job_t){ txn_cnt*(ulong)k/(ulong)nthread, txn_cnt*(ulong)(k+1)/(ulong)nthread,
-                           payload, txn_off, txn_sz, txn_err, sig_base, sig_err };
+                           payload, txn_off, txn_sz, txn_err, sig_base, sig_err, 0 };
     pthread_create( &th[ k ], NULL, txn_worker, &jb[ k ] );
   }
-  for( int k=0; k<nthread; k++ ) pthread_join( th[ k ], NULL );
-  return 0;
+  int fail = 0;
+  for( int k=0; k<nthread; k++ ) { pthread_join( th[ k ], NULL ); fail |= jb[ k ].fail; }
+  return -fail;
 }

@@ -52,6 +52,13 @@ ref_ed25519_verify_batch( uint64_t n, uint8_t const * pub, uint8_t const * sig, 
    payload does not parse (the rule of fd_ed25519_amd_verify_txns). */
 unsigned long fd_txn_parse( uint8_t const * payload, unsigned long payload_sz, void * out_buf, void * counters_opt );
 
+/* Room fd_txn_parse needs for any payload it accepts (up to 65535 B, not
+   only the 1232-B MTU that FD_TXN_MAX_SZ covers): every instruction takes
+   at least 3 payload bytes, at most 254 lookup tables.  The value of
+   FD_TXN_AMD_FOOTPRINT_MAX (include/fd_txn_amd.h, whose declaration of
+   fd_ed25519_verify this file cannot share). */
+#define REF_TXN_DESC_MAX (20UL + 10UL*(65535UL/3UL) + 8UL*254UL)
+
 typedef struct {               /* leading fields of fd_txn_t (fd_txn.h:146-272) */
   uint8_t  transaction_version, signature_cnt;
   uint16_t signature_off, message_off;
@@ -70,7 +77,7 @@ tjob( void * arg ) {
   tjob_t * j = (tjob_t *)arg;
   void * mem = aligned_alloc( 128, 256 );
   void * sha = fd_sha512_join( fd_sha512_new( mem ) );
-  void * buf = aligned_alloc( 64, 4096 );   /* >= FD_TXN_MAX_SZ */
+  void * buf = aligned_alloc( 64, (REF_TXN_DESC_MAX + 63UL) & ~63UL );
   for( uint64_t t=j->lo; t<j->hi; t++ ) {
     uint8_t const * p = j->payload + j->off[t];
     unsigned long sz = j->sz[t];

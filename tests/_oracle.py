@@ -48,6 +48,8 @@ def oracle():
         L.oracle_txn_parse.restype = ctypes.c_ulong
         L.oracle_txn_parse_fail_line.argtypes = [vp, ctypes.c_ulong]
         L.oracle_txn_parse_fail_line.restype = ctypes.c_ulong
+        L.oracle_txn_desc_max.argtypes = []
+        L.oracle_txn_desc_max.restype = ctypes.c_ulong
         L.oracle_txn_verify_batch.argtypes = [ctypes.c_ulong, vp, vp, vp, vp, vp, vp, ctypes.c_int]
         L.oracle_txn_verify_batch.restype = ctypes.c_int
         ci = ctypes.c_int
@@ -166,6 +168,8 @@ def ref():
         L.fd_sha512_join.restype = vp
         L.fd_ed25519_verify.argtypes = [vp, ctypes.c_ulong, vp, vp, vp]
         L.fd_ed25519_verify.restype = ctypes.c_int
+        L.fd_txn_parse.argtypes = [vp, ctypes.c_ulong, vp, vp]
+        L.fd_txn_parse.restype = ctypes.c_ulong
         _r = L
     return _r
 
@@ -253,13 +257,37 @@ def stream_inputs(seed, count, szlo, szhi, mixed):
     return prv, blob[:used + 1], off, sz, fk, fp
 
 
+def txn_desc_max():
+    """Room a descriptor buffer needs for any payload the parser accepts (up
+    to 65535 B): the oracle's ORACLE_TXN_DESC_MAX."""
+    return int(oracle().oracle_txn_desc_max())
+
+
+_txn_buf = None
+
+
 def txn_parse(payload):
     """oracle fd_txn_parse: (footprint, descriptor bytes[:footprint], fail line)."""
+    global _txn_buf
     p = bytes(payload)
-    buf = ctypes.create_string_buffer(3570 + 16)
-    fp = oracle().oracle_txn_parse(p if p else None, len(p), buf, None)
+    if _txn_buf is None:
+        _txn_buf = ctypes.create_string_buffer(txn_desc_max())
+    fp = oracle().oracle_txn_parse(p if p else None, len(p), _txn_buf, None)
     line = 0 if fp else oracle().oracle_txn_parse_fail_line(p if p else None, len(p))
-    return int(fp), buf.raw[:fp], int(line)
+    return int(fp), ctypes.string_at(_txn_buf, fp), int(line)
+
+
+def ref_txn_parse(payload):
+    """The compiled reference's fd_txn_parse, same triple as txn_parse (the
+    line from its counters ring); None when oracle/_ref was not built."""
+    R = ref()
+    if R is None:
+        return None
+    p = bytes(payload)
+    buf = ctypes.create_string_buffer(txn_desc_max())
+    ctr = (ctypes.c_ulong * 34)()   # fd_txn_parse_counters_t: success_cnt, failure_cnt, failure_ring[32]
+    fp = R.fd_txn_parse(p if p else None, len(p), buf, ctr)
+    return int(fp), ctypes.string_at(buf, fp), 0 if fp else int(ctr[2])
 
 
 def txn_verify_batch(payload, txn_off, txn_sz, nthread=None):
@@ -274,5 +302,6 @@ def txn_verify_batch(payload, txn_off, txn_sz, nthread=None):
     serr = np.zeros(max(payload.size // 65 + 1, 1), np.int8)
     if nthread is None:
         nthread = min(16, os.cpu_count() or 1)
-    oracle().oracle_txn_verify_batch(n, _p(payload), _p(off), _p(sz), _p(terr), _p(base), _p(serr), nthread)
+    if oracle().oracle_txn_verify_batch(n, _p(payload), _p(off), _p(sz), _p(terr), _p(base), _p(serr), nthread):
+        raise MemoryError("oracle_txn_verify_batch: no descriptor buffer")
     return terr[:n], base, serr[:int(base[-1])]

@@ -137,3 +137,160 @@ def build_txns(seed, count, nsig_lo=1, nsig_hi=12, msg_lo=64, msg_hi=1232, v0_fr
         payloads.append(bytes([n]) + sig[k:k + n].tobytes() + msgs[t])
         k += n
     return payloads, nsig
+
+
+# ---- directed payloads at the grammar limits of fd_txn_parse ----
+
+EMPTY_IX = b"\x01\x00\x00"   # program index 1, no accounts, no data
+
+
+def ins(prog, accts=b"", data=b"", nacc_raw=None, ndata_raw=None):
+    """One instruction; the *_raw arguments replace a count's compact-u16."""
+    return (bytes([prog]) + (cu16(len(accts)) if nacc_raw is None else nacc_raw) + bytes(accts) +
+            (cu16(len(data)) if ndata_raw is None else ndata_raw) + bytes(data))
+
+
+def lut(nw, nr, nw_raw=None, nr_raw=None):
+    """One address table lookup: 32-B address, nw writable and nr readonly
+    index bytes; the *_raw arguments replace a count's compact-u16."""
+    return (b"\x77" * 32 + (cu16(nw) if nw_raw is None else nw_raw) + bytes(nw) +
+            (cu16(nr) if nr_raw is None else nr_raw) + bytes(nr))
+
+
+def mk(nsig, v0, ros, rou, nacct, instrs, luts=None, tail=b"", nsig_sigs=None, ver=0x80, hdr_nsig=None,
+       nacct_raw=None, ninstr_raw=None, nlut_raw=None):
+    """A payload from its parts, fixed bytes throughout (signatures 0x11,
+    account address k is 32 bytes of k+1, blockhash 0x33).  instrs / luts are
+    lists of ins() / lut() bytes; luts=None leaves the table section out (a
+    legacy message with luts given gets one all the same).  The keyword
+    arguments override single wire fields: the version byte, the message
+    header's copy of the signature count, and the raw compact-u16 of the
+    account, instruction and table counts."""
+    nss = nsig if nsig_sigs is None else nsig_sigs
+    p = bytes([nsig]) + b"\x11" * (64 * nss)
+    if v0:
+        p += bytes([ver])
+    p += bytes([nsig if hdr_nsig is None else hdr_nsig, ros, rou])
+    p += cu16(nacct) if nacct_raw is None else nacct_raw
+    p += b"".join(bytes([(k + 1) & 0xff]) * 32 for k in range(nacct)) + b"\x33" * 32
+    p += cu16(len(instrs)) if ninstr_raw is None else ninstr_raw
+    p += b"".join(instrs)
+    if luts is not None:
+        p += cu16(len(luts)) if nlut_raw is None else nlut_raw
+        p += b"".join(luts)
+    return p + tail
+
+
+# compact-u16 encodings sent to every site: (raw bytes, decoded value or None when the decoder rejects them)
+CU16_FORMS = ((b"\x7f", 0x7f), (b"\x80\x01", 0x80), (b"\xff\x7f", 0x3fff), (b"\x80\x80\x01", 0x4000),
+              (b"\xff\xff\x03", 0xffff), (b"\x80\x00", None), (b"\x80\x80\x00", None), (b"\xff\xff\x04", None))
+CU16_SITES = ("nacct", "ninstr", "ix_nacc", "ix_ndata", "nlut", "lut_nw", "lut_nr")
+
+
+def _cu16_site(site, raw, val, cut=None):
+    """A v0 payload (1 signer, 2 accounts unless the site is the account
+    count) whose compact-u16 at `site` is `raw`, followed by as much of what
+    the decoded value `val` announces as a 65535-B payload can hold, capped
+    (None: nothing).  cut: end the payload after that many bytes of raw."""
+    v = val or 0
+    if site == "nacct":
+        p = mk(1, True, 0, 0, min(v, 256), [ins(1)], [], nacct_raw=raw)
+    elif site == "ninstr":
+        p = mk(1, True, 0, 0, 2, [EMPTY_IX] * min(v, 21000), [], ninstr_raw=raw)
+    elif site == "ix_nacc":
+        p = mk(1, True, 0, 0, 2, [ins(1, accts=bytes(min(v, 60000)), nacc_raw=raw)], [])
+    elif site == "ix_ndata":
+        p = mk(1, True, 0, 0, 2, [ins(1, data=bytes(min(v, 60000)), ndata_raw=raw)], [])
+    elif site == "nlut":
+        p = mk(1, True, 0, 0, 2, [ins(1)], [lut(0, 0)] * min(v, 1500), nlut_raw=raw)
+    elif site == "lut_nw":
+        p = mk(1, True, 0, 0, 2, [ins(1)], [lut(min(v, 20000), 0, nw_raw=raw)])
+    else:
+        p = mk(1, True, 0, 0, 2, [ins(1)], [lut(0, min(v, 20000), nr_raw=raw)])
+    if cut is None:
+        return p
+    # offset of the site: count byte, signature, version + 3 header bytes, ...
+    head = {"nacct": 1 + 64 + 4,
+            "ninstr": 1 + 64 + 4 + 1 + 64 + 32,
+            "ix_nacc": 1 + 64 + 4 + 1 + 64 + 32 + 1 + 1,
+            "ix_ndata": 1 + 64 + 4 + 1 + 64 + 32 + 1 + 1 + 1,
+            "nlut": 1 + 64 + 4 + 1 + 64 + 32 + 1 + 3,
+            "lut_nw": 1 + 64 + 4 + 1 + 64 + 32 + 1 + 3 + 1 + 32,
+            "lut_nr": 1 + 64 + 4 + 1 + 64 + 32 + 1 + 3 + 1 + 32 + 1}[site]
+    assert p[head:head + len(raw)] == raw, site
+    return p[:head + cut]
+
+
+# name -> (footprint, 0) for a case the reference accepts, (0, line of
+# fd_txn_parse.c) for one it rejects.  Cases not named here (the compact-u16
+# forms) expect whatever the oracle says.
+LIMIT_EXPECT = {}
+LIMIT_SIZE = {"max_size": 65535, "max_size_plus1": 65536, "max_size_trailing": 65535, "mtu_355_instr": 1232,
+              "instr_356": 1235, "sig_127": 12230}
+_limit_cases = None
+
+
+def limit_cases():
+    """[(name, payload)]: directed payloads at the limits of the transaction
+    grammar, deterministic.  LIMIT_EXPECT holds the reference's verdict of
+    the named ones, LIMIT_SIZE the size of those whose size is the point."""
+    global _limit_cases
+    if _limit_cases is not None:
+        return _limit_cases
+    out = []
+
+    def add(name, payload, fp=0, line=0):
+        assert (fp == 0) != (line == 0) and name not in LIMIT_EXPECT
+        LIMIT_EXPECT[name] = (fp, line)
+        out.append((name, payload))
+
+    # sizes
+    big = mk(1, False, 0, 0, 2, [EMPTY_IX] * 21789)
+    add("max_size", big, fp=20 + 10 * 21789)
+    add("max_size_plus1", big + b"\0", line=73)
+    add("max_size_trailing", mk(1, False, 0, 0, 2, [EMPTY_IX] * 21787 + [ins(1, data=b"\0\0")], tail=b"\0"), line=189)
+    add("mtu_355_instr", mk(1, False, 0, 0, 2, [EMPTY_IX] * 355), fp=3570)
+    add("instr_356", mk(1, False, 0, 0, 2, [EMPTY_IX] * 356), fp=3580)
+    add("instr_350_lut_20", mk(1, True, 0, 0, 2, [EMPTY_IX] * 350, [lut(1, 1)] * 20), fp=20 + 3500 + 160)
+    # signature count
+    add("sig_127", mk(127, False, 0, 0, 127, []), fp=20)
+    add("sig_128", mk(128, False, 0, 0, 128, []), line=81)
+    add("sig_0", mk(0, False, 0, 0, 1, []), line=81)
+    add("ros_eq_nsig", mk(2, False, 2, 0, 3, [ins(1)]), line=100)
+    add("nsig_rou_eq_nacct", mk(2, False, 0, 1, 3, [ins(1)]), fp=30)
+    add("nsig_rou_eq_nacct_plus1", mk(2, False, 0, 2, 3, [ins(1)]), line=107)
+    # account count
+    add("acct_127", mk(1, False, 0, 0, 127, [ins(126, accts=b"\x7e")]), fp=30)
+    add("acct_128", mk(1, False, 0, 0, 128, [ins(127, accts=b"\x7f")]), fp=30)
+    add("acct_256", mk(1, False, 0, 0, 256, [ins(255, accts=b"\xff")]), fp=30)
+    add("acct_257", mk(1, False, 0, 0, 257, [ins(1)]), line=106)
+    # lookup tables
+    add("lut_254", mk(1, True, 0, 0, 1, [], [lut(0, 0)] * 254), fp=20 + 8 * 254)
+    add("lut_255", mk(1, True, 0, 0, 1, [], [lut(0, 0)] * 255), line=162)
+    add("lut_w255_acct1", mk(1, True, 0, 0, 1, [], [lut(255, 0)]), fp=28)
+    add("lut_w255_r1_acct1", mk(1, True, 0, 0, 1, [], [lut(255, 1)]), line=191)
+    add("lut_w256", mk(1, True, 0, 0, 1, [], [lut(256, 0)]), line=175)
+    add("lut_200_55_acct2", mk(1, True, 0, 0, 2, [], [lut(200, 0), lut(55, 0)]), line=191)
+    add("lut_w_eq_256_minus_nacct", mk(1, True, 0, 0, 16, [], [lut(240, 0)]), fp=28)
+    # account indices: 2 accounts and a table adding 4, so 6 in all
+    t4 = [lut(2, 2)]
+    add("index_5_5", mk(1, True, 0, 0, 2, [ins(5, accts=b"\x05")], t4), fp=38)
+    add("index_prog_6", mk(1, True, 0, 0, 2, [ins(6, accts=b"\x05")], t4), line=200)
+    add("index_acct_6", mk(1, True, 0, 0, 2, [ins(5, accts=b"\x06")], t4), line=202)
+    add("index_prog_0", mk(1, True, 0, 0, 2, [ins(0, accts=b"\x05")], t4), line=200)
+    # other
+    add("trailing_byte", mk(1, False, 0, 0, 2, [ins(1)], tail=b"\0"), line=189)
+    add("legacy_with_tables", mk(1, False, 0, 0, 2, [ins(1)], [lut(1, 1)]), line=189)
+    add("version_0x81", mk(1, True, 0, 0, 2, [ins(1)], [], ver=0x81), line=91)
+    add("v0_count_mismatch", mk(2, True, 0, 0, 2, [ins(1)], [], hdr_nsig=1), line=93)
+    # every compact-u16 form at every site, whole and cut short
+    for site in CU16_SITES:
+        cuts = set()
+        for raw, val in CU16_FORMS:
+            out.append(("cu16_%s_%s" % (site, raw.hex()), _cu16_site(site, raw, val)))
+            for cut in range(1, len(raw)):
+                if raw[:cut] not in cuts:
+                    cuts.add(raw[:cut])
+                    out.append(("cu16_%s_%s_cut" % (site, raw[:cut].hex()), _cu16_site(site, raw, val, cut)))
+    _limit_cases = out
+    return out

@@ -135,3 +135,65 @@ def test_oracle_multisigner_rule_matches_compiled_reference():
     terr, _, _ = _oracle.txn_verify_batch(blob, off, sz)
     assert np.array_equal(err, terr)
     assert (err != 0).sum() >= 20
+
+
+# ---- the grammar limits (tests/_txn.py: limit_cases) ----
+
+@pytest.fixture(scope="module")
+def limits():
+    """[(name, payload, (footprint, descriptor, line))] by the oracle, computed once."""
+    return [(n, p, _oracle.txn_parse(p)) for n, p in _txn.limit_cases()]
+
+
+def test_limit_cases_premise(limits):
+    """Every named limit case gets, from the oracle, the verdict written
+    beside it (footprint of an accepted case, fd_txn_parse.c line of a
+    rejected one) and has the size that is its point: a slip in the builder
+    cannot quietly turn a limit case into an early reject.  Every
+    compact-u16 form is present at every site."""
+    names = [n for n, _, _ in limits]
+    assert len(set(names)) == len(names) and set(_txn.LIMIT_EXPECT) <= set(names)
+    got = {n: (fp, line) for n, _, (fp, _, line) in limits if n in _txn.LIMIT_EXPECT}
+    assert got == _txn.LIMIT_EXPECT
+    assert {n: len(p) for n, p, _ in limits if n in _txn.LIMIT_SIZE} == _txn.LIMIT_SIZE
+    assert _txn.LIMIT_EXPECT["max_size"] == (217910, 0)
+    for site in _txn.CU16_SITES:
+        for raw, val in _txn.CU16_FORMS:
+            assert "cu16_%s_%s" % (site, raw.hex()) in names
+        for cut in ("80", "ff", "8080", "ffff"):
+            assert "cu16_%s_%s_cut" % (site, cut) in names
+    # the decoder's own verdict where the grammar lets a form through: the
+    # three in-range forms that fit are accepted at the sites without a cap
+    ok = {n for n, _, (fp, _, _) in limits if fp}
+    for site in ("ix_nacc", "ix_ndata"):
+        assert {"cu16_%s_%s" % (site, f) for f in ("7f", "8001", "ff7f", "808001")} <= ok
+    assert _oracle.txn_desc_max() >= max(fp for _, _, (fp, _, _) in limits)
+
+
+def test_limit_cases_oracle_matches_compiled_reference(limits):
+    """libfdref.so's fd_txn_parse (the reference's own source, compiled)
+    agrees with the oracle on every limit case: footprint, descriptor bytes
+    [0, footprint) and failing line."""
+    if _oracle.ref() is None:
+        pytest.skip("oracle/_ref not built")
+    for n, p, want in limits:
+        assert _oracle.ref_txn_parse(p) == want, n
+
+
+def test_txn_slots_matches_oracle_sig_base(limits):
+    """fd_ed25519_amd_txn_slots (the host rule that sizes the signature
+    slots) equals the oracle's sig_base on every limit case and at the
+    signature counts 0 / 127 / 128, with and without room for the
+    signatures, and on an empty payload."""
+    from firedancer_amd import ed25519
+    pays = [p for _, p, _ in limits]
+    pays += [b"", b"\x00", b"\x00" + bytes(64), b"\x7f", b"\x7f" + bytes(64 * 127), b"\x7f" + bytes(64 * 127 - 1),
+             b"\x80" + bytes(64 * 128), b"\x01" + bytes(64), b"\x01" + bytes(63)]
+    blob, off, sz = _txn.pack(pays)
+    base, tot = ed25519.txn_slots(blob, off, sz)
+    _, ebase, _ = _oracle.txn_verify_batch(blob, off, sz)
+    assert np.array_equal(base, ebase) and tot == int(ebase[-1])
+    extra = np.diff(base.astype(np.int64))[len(limits):].tolist()
+    assert extra == [0, 0, 0, 0, 127, 0, 0, 1, 0]
+    by_name = dict(zip((n for n, _, _ in limits), np.diff(base.astype(np.int64)).tolist()))
+    assert (by_name["sig_127"], by_name["sig_128"], by_name["sig_0"]) == (127, 0, 0)
