@@ -157,7 +157,6 @@ inline ulong now_ns( void ) {
 } /* namespace */
 
 #define FRAME_CHUNKS ((uint)(FD_VERIFY_AMD_FRAME_SZ >> FD_CHUNK_LG_SZ))
-#define FRAME_FREE   (~0UL)
 #define TXN_SIG_MAX_AT_MTU (19UL)   /* most signatures fd_amd_txn_slots1 reserves for a 1232-B payload */
 #define STAGE_PASS   (256UL)        /* frags staged per pass of the run loop before it hands over */
 #define CHUNK_SLOTS  (64UL)         /* signature slots of a throughput chunk (one lane each) */
@@ -335,10 +334,12 @@ struct fd_verify_amd_tile {
   uint8_t *          out_base;
   uint8_t *          out_dev;
   ulong              frame_cnt;
-  std::vector<ulong> frame_pub;  /* out seq of the frag a frame last carried (FRAME_FREE: none) */
+  std::vector<ulong> frame_pub;  /* out seq of the frag a frame last carried; any 64-bit value is a live sequence */
+  std::vector<uint8_t> frame_held;  /* 1: frame_pub holds (a consumer may still read the frame); 0: carried none */
   uint8_t *          frame_busy; /* 1 while a frame is staged, in flight, or orphaned (stager sets, publisher clears) */
   ulong              frame_next_idx;   /* next frame to reserve (cyclic) */
   ulong              out_seq_end;   /* out seq after the last run's last publish (a run continuing it keeps frame_pub) */
+  bool               out_seq_end_ok;   /* a run has set out_seq_end */
   /* persistent consumer (k_tile_persist) */
   bool                 persist_ok;  /* its resources are allocated */
   hipStream_t          pst;
@@ -686,9 +687,10 @@ fd_verify_amd_tile_new_cfg( fd_verify_amd_tile_cfg_t const * cfg ) {
   bool ok = hipHostMalloc( (void **)&t->out_base, c.out_frame_cnt * FD_VERIFY_AMD_FRAME_SZ, hipHostMallocMapped ) == hipSuccess &&
             hipHostGetDevicePointer( (void **)&t->out_dev, t->out_base, 0 ) == hipSuccess;
   t->frame_cnt = c.out_frame_cnt;
-  t->frame_pub.assign( c.out_frame_cnt, FRAME_FREE );
+  t->frame_pub.assign( c.out_frame_cnt, 0UL );
+  t->frame_held.assign( c.out_frame_cnt, (uint8_t)0 );
   t->frame_busy = (uint8_t *)calloc( c.out_frame_cnt, 1 );
-  t->out_seq_end = ~0UL;
+  t->out_seq_end = 0UL; t->out_seq_end_ok = false;
   if( !ok || !t->frame_busy || !tile_count( t, true ) ) {
     if( ok && t->frame_busy ) fprintf( stderr, "fd_verify_amd_tile_new: device %d already runs %d tiles in this process "
                                        "(one hardware queue each, GPU_MAX_HW_QUEUES)\n", c.device, tile_queue_max() );
@@ -943,7 +945,7 @@ publish_pass( prun_t & r ) {
       }
     }
     ulong const f = m.fidx;
-    t->frame_pub[f] = r.out_seq;
+    t->frame_pub[f] = r.out_seq; t->frame_held[f] = 1u;   /* before frame_busy's release below */
     fd_mcache_publish( r.out_mcache, r.out_depth, r.out_seq, t->res[j], f * FRAME_CHUNKS, m.sz, m.ctl, m.tsorig, tspub );
     __atomic_store_n( &t->frame_busy[f], (uint8_t)0, __ATOMIC_RELEASE );
     if( r.lat_n < r.lat_max ) {
@@ -1036,7 +1038,8 @@ tile_run_persist( fd_verify_amd_tile_t * t, fd_frag_meta_t const * in_mcache, ul
   r.zc = zc_dev != NULL; r.lat = lat; r.lat_max = (lat || t->trace) ? std::max( lat ? lat_max : 0UL, t->trace_max ) : 0UL;
   if( lat && t->trace ) r.lat_max = std::min( lat_max, t->trace_max );
   r.mask = mask; r.R = t->R; r.H = H;
-  r.pubd = base; r.out_seq = out_seq0; r.lat_n = 0UL; r.out_cr = 0UL; r.t_halt = 0UL;
+  r.pubd = base; r.out_seq = out_seq0; r.lat_n = 0UL; r.t_halt = 0UL;
+  r.out_cr = out_seq0;   /* no credit yet: the first publish loads it, whatever the origin */
   r.g_off = r.g_off_cur = 0L; r.g_win = 0UL; r.g_last = 0UL; r.g_ok = false;
   memset( &r.d, 0, sizeof r.d );
   r.handed.store( base ); r.pubd_a.store( base ); r.end.store( ~0UL ); r.quit.store( 0 ); r.halt.store( 0 );
@@ -1096,7 +1099,11 @@ tile_run_persist( fd_verify_amd_tile_t * t, fd_frag_meta_t const * in_mcache, ul
 
   ulong in_seq = in_seq0, staged = base, handed = base;
   ulong staged_sl = 0UL, handed_sl = 0UL;   /* signature slots staged / handed over in this run */
-  ulong in_cnt = diag->in_cnt, cons = out_seq0, fseq_pub = ~0UL;
+  /* cons: the consumer's position as last read.  A run that continues an
+     output session may start ahead of a lagging consumer, whose unread frags
+     sit in frames of the previous run: it starts from out_fseq, not out_seq0 */
+  ulong in_cnt = diag->in_cnt, cons = out_fseq ? __atomic_load_n( out_fseq, __ATOMIC_ACQUIRE ) : out_seq0, fseq_pub = 0UL;
+  bool fseq_set = false;                 /* fseq_pub holds what in_fseq was last given */
   ulong ovrn = 0, bad = 0, ha = 0, ha_sz = 0, backp = 0, nbatch = 0, nsig = 0, switches = 0;
   ulong cdone = dbase;                   /* first descriptor not known to be finished */
   ulong n_pass = 0, n_hand = 0, n_stop_window = 0, n_stop_frames = 0, n_stop_bmax = 0, n_stop_pass = 0, n_steal = 0;
@@ -1138,12 +1145,12 @@ tile_run_persist( fd_verify_amd_tile_t * t, fd_frag_meta_t const * in_mcache, ul
     ulong const f = t->frame_next_idx;
     *credit = false;
     if( __atomic_load_n( &t->frame_busy[f], __ATOMIC_ACQUIRE ) ) return false;
-    if( out_fseq && t->frame_pub[f] != FRAME_FREE && (long)(t->frame_pub[f] - cons) >= 0 ) {
+    if( out_fseq && t->frame_held[f] && (long)(t->frame_pub[f] - cons) >= 0 ) {
       cons = __atomic_load_n( out_fseq, __ATOMIC_ACQUIRE );
       if( (long)(t->frame_pub[f] - cons) >= 0 ) { *credit = true; return false; }
     }
     t->frame_busy[f] = 1u;
-    t->frame_pub[f] = FRAME_FREE;
+    t->frame_held[f] = 0u;
     if( ++t->frame_next_idx == F ) t->frame_next_idx = 0UL;
     *fo = (uint)f;
     return true;
@@ -1153,7 +1160,10 @@ tile_run_persist( fd_verify_amd_tile_t * t, fd_frag_meta_t const * in_mcache, ul
      whose source an orphaned helper block may still be reading */
   auto copy_rel = [&]() -> ulong {
     ulong rel = pend.on ? pend.seq0 : in_seq;   /* a posted pass is not copied yet */
-    for( orphan_t const & o : orphans ) rel = std::min( rel, cp->jobs[o.s][o.b * cp->bsz[o.s].load( std::memory_order_relaxed )].seq );
+    for( orphan_t const & o : orphans ) {   /* the oldest, by distance behind in_seq (sequences wrap) */
+      ulong const os = cp->jobs[o.s][o.b * cp->bsz[o.s].load( std::memory_order_relaxed )].seq;
+      if( (long)(os - in_seq) < (long)(rel - in_seq) ) rel = os;
+    }
     return rel;
   };
   /* re-check each copied frag's mcache line and stage it, in input order */
@@ -1253,7 +1263,7 @@ tile_run_persist( fd_verify_amd_tile_t * t, fd_frag_meta_t const * in_mcache, ul
        zero copy once it is published (or dropped) */
     if( in_fseq ) {
       ulong rel = !zc_dev ? copy_rel() : pubd == staged ? in_seq : t->ppend[pubd & mask].seq;
-      if( rel != fseq_pub ) { __atomic_store_n( in_fseq, rel, __ATOMIC_RELEASE ); fseq_pub = rel; }
+      if( !fseq_set || rel != fseq_pub ) { __atomic_store_n( in_fseq, rel, __ATOMIC_RELEASE ); fseq_pub = rel; fseq_set = true; }
     }
     /* after *stop: drain what was taken in; give up only if the publisher
        reports the output backpressured past the halt grace */
@@ -1370,7 +1380,7 @@ tile_run_persist( fd_verify_amd_tile_t * t, fd_frag_meta_t const * in_mcache, ul
        an orphaned helper block may still be reading */
     if( in_fseq && !zc_dev ) {
       ulong const rel = copy_rel();
-      if( rel != fseq_pub ) { __atomic_store_n( in_fseq, rel, __ATOMIC_RELEASE ); fseq_pub = rel; }
+      if( !fseq_set || rel != fseq_pub ) { __atomic_store_n( in_fseq, rel, __ATOMIC_RELEASE ); fseq_pub = rel; fseq_set = true; }
     }
     done_in = done_in || (frag_cnt && in_seq - in_seq0 >= frag_cnt);
 
@@ -1583,7 +1593,7 @@ tile_run_persist( fd_verify_amd_tile_t * t, fd_frag_meta_t const * in_mcache, ul
   t->ph_frags = ph_frags;
   __atomic_store_n( &diag->in_cnt, in_cnt, __ATOMIC_RELEASE );
   if( in_fseq ) __atomic_store_n( in_fseq, in_seq, __ATOMIC_RELEASE );
-  t->out_seq_end = r.out_seq;
+  t->out_seq_end = r.out_seq; t->out_seq_end_ok = true;
   return rc;
 }
 
@@ -1601,7 +1611,7 @@ fd_verify_amd_tile_run( fd_verify_amd_tile_t * t, fd_frag_meta_t const * in_mcac
      consumer may still read is not reused before out_fseq passes it; any
      other out_seq0 starts a new session (a new consumer), with every frame
      free. */
-  if( out_seq0 != t->out_seq_end ) std::fill( t->frame_pub.begin(), t->frame_pub.end(), FRAME_FREE );
+  if( !t->out_seq_end_ok || out_seq0 != t->out_seq_end ) std::fill( t->frame_held.begin(), t->frame_held.end(), (uint8_t)0 );
   t->frame_next_idx = 0UL;
 
   /* zero copy: the input data region is mapped into the GPU; frags are

@@ -51,12 +51,16 @@ def _aligned(nbytes, align=64):
     return raw[off:off + nbytes]
 
 
-def mcache_new(depth):
-    """An mcache ring of `depth` (power of 2) frag metadata, every line
-    marked "not yet published" for the first lap (seq = line - depth)."""
+def mcache_new(depth, seq0=0):
+    """An mcache ring of `depth` (power of 2) frag metadata whose first frag
+    will be seq0 (any 64-bit value), every line marked "older than seq0" the
+    way fd_mcache_new does: line s & (depth-1) holds s for s in
+    [seq0-depth, seq0), mod 2^64 (seq0 0: seq = line - depth)."""
     assert depth and not depth & (depth - 1)
     m = _aligned(32 * depth).view(FRAG_META)
-    m["seq"] = (np.arange(depth, dtype=np.int64) - depth).astype(np.uint64)
+    line = np.arange(depth, dtype=np.uint64)
+    lo = np.uint64((seq0 - depth) & 0xFFFFFFFFFFFFFFFF)
+    m["seq"] = lo + ((line - lo) & np.uint64(depth - 1))       # uint64 arithmetic wraps
     return m
 
 

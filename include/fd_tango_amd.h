@@ -305,7 +305,9 @@ fd_verify_amd_tile_register_dcache( fd_verify_amd_tile_t * tile, void * base, ul
    223-274).  Input:
    in_mcache (depth in_depth, power of 2), in_chunk0 = local address of
    chunk 0 of the input data region (fd_chunk_to_laddr), first sequence
-   number in_seq0.  in_fseq (NULL = none) receives the tile's flow-control
+   number in_seq0.  in_seq0 and out_seq0 may be any 64-bit value: sequence
+   numbers wrap from 2^64-1 to 0 and are compared modulo 2^64, as in
+   tango.  in_fseq (NULL = none) receives the tile's flow-control
    sequence for the producer (the reference's fseq, fd_fseq_update): every
    input frag below it is no longer read by the tile, so the producer may
    reuse its mcache line and its data.  Output: out_mcache (depth

@@ -165,3 +165,25 @@ def test_level_step_holds():
     st[0] = st[1] = st[2] = st[3] = 0
     assert s(T, L, 0) == T and s(T, L, H) == L             # time 0 is a time like any other
     assert step(Q, T, 0, H, None) == T and step(T, L, 0, H, None) == L   # no state: no holds
+
+
+@pytest.mark.parametrize("seq0", [0, 3, 12345, (1 << 63) - 40, 1 << 63, (1 << 64) - 100, (1 << 64) - 1])
+@pytest.mark.parametrize("depth", [1, 8, 1024])
+def test_mcache_new_marks_every_line_older_than_seq0(depth, seq0):
+    """tango.mcache_new, as fd_mcache_new: line s & (depth-1) holds s for the
+    depth sequence numbers s before seq0 (mod 2^64), so a consumer waiting
+    for seq0 reads every line as not yet published; publish then replaces
+    exactly its own line.  seq0 0 is the layout it always had."""
+    import numpy as np
+    m64 = (1 << 64) - 1
+    mc = tango.mcache_new(depth, seq0)
+    assert mc.size == depth and mc["seq"].dtype == np.dtype("<u8")
+    want = {(seq0 - 1 - j) & m64 for j in range(depth)}
+    assert {int(s) for s in mc["seq"]} == want
+    assert all(int(s) & (depth - 1) == line for line, s in enumerate(mc["seq"]))
+    if seq0 == 0:
+        assert np.array_equal(mc["seq"], (np.arange(depth, dtype=np.int64) - depth).astype(np.uint64))
+        assert np.array_equal(mc["seq"], tango.mcache_new(depth)["seq"])
+    tango.publish(mc, seq0, 7, 1, 2, 3, 4, 5)
+    assert int(mc[seq0 & (depth - 1)]["seq"]) == seq0
+    assert {int(s) for s in mc["seq"]} == (want - {(seq0 - depth) & m64}) | {seq0}
