@@ -118,6 +118,8 @@ fd_ed25519_amd_new( int device, ulong batch_max, ulong blob_max ) {
   fd_ed25519_amd_t * e = (fd_ed25519_amd_t *)calloc( 1, sizeof(fd_ed25519_amd_t) );
   if( !e ) return NULL;
   e->device = device; e->cap = batch_max; e->blob_cap = blob_max; e->nslot = nslot;
+  ev = getenv( "FD_ED25519_AMD_GATHER_COPY" );
+  e->gather_copy = ev && atoi( ev ) == 1;
   /* the pinned staging on the GPU's NUMA node (the thread's own policy is
      restored afterwards; fd_numa.cpp) */
   int pmode = 0; unsigned long pmask[16];
@@ -590,6 +592,141 @@ fd_ed25519_amd_verify_soa_registered_tag( fd_ed25519_amd_t * e, ulong n, uchar c
       rc = slot_launch_packed( s, ch.c, soa_stage( s, ch, pub + 32UL*i, sig + 64UL*i, msg_off + i, msg_sz + i, blob, false ),
                                err + i, tg );
     return rc ? rc : (long)ch.c;
+  } );
+}
+
+/* ------------------------------------------------------------------ */
+/* pointer-array batches gathered by the GPU from registered memory     */
+
+/* The one place that sizes a gathered chunk: of n signatures with message
+   sizes sz[], a chunk takes the first (every message fits a chunk: the
+   callers check sz <= blob_max up front) and further ones while their
+   count stays <= cap and the padded total, the sum of round_up( sz, 16 ),
+   stays <= blob_cap.  dst[j]: message j's offset in the chunk's blob, a
+   multiple of 16; it owns [dst[j], dst[j] + round_up( sz[j], 16 )).
+   Returns the signatures taken.  Pure host code. */
+extern "C" ulong
+fd_ed25519_amd_gather_layout( ulong n, ulong const * sz, ulong cap, ulong blob_cap, uint * dst ) {
+  ulong c = 0, b = 0;
+  while( c < n ) {
+    ulong const pad = (sz[c] + 15UL) & ~15UL;
+    if( c && ( c >= cap || sz[c] > blob_cap || b + pad > blob_cap ) ) break;
+    dst[c] = (uint)b;
+    b += pad; c++;
+  }
+  return c;
+}
+
+namespace {
+/* The registration table as one call sees it: copied under g_reg_mu once,
+   then searched without the lock, the last hit first (the frags of one
+   dcache all lie in one registration). */
+struct reg_view_t {
+  std::vector<reg_t> reg;
+  size_t             last = 0;
+  reg_view_t() { std::lock_guard<std::mutex> g( g_reg_mu ); reg = g_reg; }
+  /* [p, p+sz), sz > 0, lies in one registration of the table: *dev = p's device address */
+  bool xlat( void const * p, ulong sz, uint64_t * dev ) {
+    uintptr_t const a = (uintptr_t)p, b = a + sz;
+    if( b <= a || reg.empty() ) return false;
+    reg_t const * r = &reg[last];
+    if( !( a >= r->lo && b <= r->hi ) ) {
+      size_t k = 0;
+      while( k < reg.size() && !( a >= reg[k].lo && b <= reg[k].hi ) ) k++;
+      if( k == reg.size() ) return false;
+      last = k; r = &reg[k];
+    }
+    *dev = (uint64_t)(r->dev + (a - r->lo));
+    return true;
+  }
+  bool rec( fd_amd_gather_rec_t * o, void const * pub, void const * sig, void const * msg, ulong sz ) {
+    o->msg = 0UL; o->sz = (uint32_t)sz;
+    return pub && sig && xlat( pub, 32UL, &o->pub ) && xlat( sig, 64UL, &o->sig ) && ( !sz || ( msg && xlat( msg, sz, &o->msg ) ) );
+  }
+};
+}
+
+/* Chunk of c signatures whose records sit in s->h_pack: k_gather fetches
+   them into the slot's planes, then the pipeline of slot_launch_dma.  The
+   records reach the kernel in place (it reads the mapped h_pack, 32 B per
+   signature, once) or, with copy, by one H2D into d_pack. */
+static int
+slot_launch_gather( slot_t * s, ulong c, bool copy, schar * out, ulong * tag ) {
+  fd_amd_gather_rec_t const * d_rec = (fd_amd_gather_rec_t const *)s->m_pack;
+  if( copy ) {
+    HIPCHK( hipMemcpyAsync( s->d_pack, s->h_pack, 32UL*c, hipMemcpyHostToDevice, s->stream ) );
+    d_rec = (fd_amd_gather_rec_t const *)s->d_pack;
+  }
+  bool const lat = fd_amd_uses_latency_path( (uint32_t)c, 0 ) != 0;
+  /* A throughput chunk's gather runs beside the other slot's verify kernels,
+     and its reads of host memory, while on their way, hold up those kernels'
+     own memory traffic: 2^20 x 200 B in 16 chunks took 32.5 ms with one wave
+     per 16 records (4096 waves a chunk), 29.6 at 256 waves, 26.0 at 128, 23.4
+     at 64, 28.9 at 32 (a lone 2^16 chunk: 2.2-2.3 ms down to 64 waves, 2.5 at
+     32: 64 waves still keep the link busy).  A latency-path batch is one
+     chunk with nothing beside it: no cap. */
+  if( fd_amd_launch_gather( (uint32_t)c, d_rec, s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_blob, lat ? 0u : 64u, s->stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  if( fd_amd_launch_verify( (uint32_t)c, s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_blob, s->d_err, s->d_ws, s->stream,
+                            1, NULL, NULL, 0, lat ? (int8_t *)s->m_err : NULL, s->strict ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  if( !lat ) HIPCHK( slot_out( s, s->m_err, s->d_err, c ) );
+  if( tag && slot_tags( s, c ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  HIPCHK( hipEventRecord( s->done, s->stream ) );
+  slot_in_flight( s, out, tag, c );
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" int
+fd_ed25519_amd_verify_batch_registered( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
+                                        void const * const * sig, void const * const * pub, schar * err ) {
+  return fd_ed25519_amd_verify_batch_registered_tag( e, n, msg, sz, sig, pub, err, NULL );
+}
+
+extern "C" int
+fd_ed25519_amd_verify_batch_registered_tag( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
+                                            void const * const * sig, void const * const * pub, schar * err,
+                                            ulong * tag ) {
+  if( !e || (n && (!msg || !sz || !sig || !pub || !err)) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !n ) return FD_ED25519_AMD_OK;
+  reg_view_t view;
+  /* every signature before anything launches: its pointers, its size, and
+     the first and last byte of each range in one registration of the table */
+  auto check = [&]( ulong lo, ulong hi ) -> bool {
+    reg_view_t v = view;                     /* its own last-hit index */
+    fd_amd_gather_rec_t probe;
+    for( ulong j=lo; j<hi; j++ )
+      if( sz[j] > e->blob_cap || !v.rec( &probe, pub[j], sig[j], msg[j], sz[j] ) ) return false;
+    return true;
+  };
+  /* the pass reads 32 B of pointers and sizes per signature and nothing of
+     it overlaps the GPU: large batches split it over up to 4 host threads,
+     as copy_par does the staging copies */
+  int nt = (int)( n >> 17 ); if( nt > 4 ) nt = 4;
+  if( nt < 2 ) { if( !check( 0UL, n ) ) return FD_ED25519_AMD_ERR_INVAL; }
+  else {
+    std::thread th[3]; bool ok[4];
+    ulong const part = ( n + (ulong)nt - 1UL ) / (ulong)nt;
+    for( int t=1; t<nt; t++ ) th[t-1] = std::thread( [&, t]{ ok[t] = check( part*(ulong)t, std::min( n, part*(ulong)(t+1) ) ); } );
+    ok[0] = check( 0UL, part );
+    for( int t=1; t<nt; t++ ) th[t-1].join();
+    for( int t=0; t<nt; t++ ) if( !ok[t] ) return FD_ED25519_AMD_ERR_INVAL;
+  }
+  return run_ring( e, e->nslot, n, [&]( slot_t * s, ulong i ) -> long {
+    if( tag ) { int rc = slot_alloc_tag( s, e->cap ); if( rc ) return rc; }
+    /* the chunk's records in h_pack (32 B per signature), their dst behind them */
+    fd_amd_gather_rec_t * rec = (fd_amd_gather_rec_t *)s->h_pack;
+    uint * dst = (uint *)(s->h_pack + 32UL*e->cap);
+    ulong c = fd_ed25519_amd_gather_layout( n - i, sz + i, e->cap, e->blob_cap, dst );
+    for( ulong j=0; j<c; j++ ) {
+      /* translated again, not kept from the check: the chunk's translation
+         runs beside the previous chunk's kernels, a table of n records would
+         not; an address the table does not give never reaches the kernel */
+      if( sz[i+j] > e->blob_cap || !view.rec( rec + j, pub[i+j], sig[i+j], msg[i+j], sz[i+j] ) ) return FD_ED25519_AMD_ERR_INVAL;
+      rec[j].dst = dst[j];
+    }
+    int rc = slot_launch_gather( s, c, e->gather_copy != 0, err + i, tag ? tag + i : NULL );
+    return rc ? rc : (long)c;
   } );
 }
 

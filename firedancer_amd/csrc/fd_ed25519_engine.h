@@ -56,6 +56,8 @@ struct fd_ed25519_amd {
   ulong  blob_cap;   /* message bytes per chunk */
   int    nslot;      /* slots the SoA calls keep in flight: 2 (double buffering), or FD_ED25519_AMD_NSLOT */
   int    mode;       /* FD_ED25519_AMD_MODE_*: mirrored into every slot's `strict` */
+  int    gather_copy;/* verify_batch_registered: 0 k_gather reads a chunk's records in the mapped h_pack (default),
+                        1 they go to d_pack by one H2D first (FD_ED25519_AMD_GATHER_COPY=1: the A/B of tools/batch_registered_cost.py) */
   slot_t slot[FD_AMD_SLOT_MAX];
 };
 

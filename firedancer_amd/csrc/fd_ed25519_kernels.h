@@ -164,6 +164,18 @@ int fd_amd_launch_rprime( uint32_t n, void const * d_ws, int kind, int32_t * d_x
 /* d_off[i] -= lo for every nonempty message (0 for empty ones). */
 int fd_amd_launch_rebase_off( uint32_t n, uint32_t * d_off, uint32_t const * d_sz, uint32_t lo, hipStream_t stream );
 
+/* k_gather (fd_ed25519_gather.h): n records -> the verify planes.  A record
+   is one signature of a pointer-array chunk: the DEVICE addresses of its
+   public key (32 B), signature (64 B) and message (sz B; unused when sz is
+   0), any byte alignment, in host memory the GPU can read; dst: a multiple
+   of 16, the message's offset in d_blob, which owns
+   [dst, dst + round_up( sz, 16 )) there.  d_rec: 32-aligned device or mapped
+   host memory.  Writes d_pub[32 i], d_sig[64 i], d_off[i] = dst,
+   d_sz[i] = sz, d_blob[dst ..]. */
+typedef struct { uint64_t pub, sig, msg; uint32_t sz, dst; } fd_amd_gather_rec_t;
+int fd_amd_launch_gather( uint32_t n, fd_amd_gather_rec_t const * d_rec, uint8_t * d_pub, uint8_t * d_sig,
+                          uint32_t * d_off, uint32_t * d_sz, uint8_t * d_blob, uint32_t waves, hipStream_t stream );
+
 /* n bytes device -> mapped host memory by a kernel (no DMA engine). */
 int fd_amd_launch_copy_out( void * d_dst_mapped, void const * d_src, size_t n, hipStream_t stream );
 

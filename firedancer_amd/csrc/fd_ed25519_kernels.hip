@@ -28,6 +28,7 @@
  *   fd_ed25519_pool.h   k_ai, k_dsmp, k_fin (large batches)
  *   fd_ed25519_tile.h   k_tile_persist, k_tile_synth
  *   fd_ed25519_strict.h k_strict (strict mode's overlay, after the DSM stage)
+ *   fd_ed25519_gather.h k_gather (pointer-array chunks from registered memory)
  * This file keeps the launch code, the batch-size policy and the small
  * kernels that move results out (k_copy_out: verdicts; k_tag_out /
  * k_tag_gather: the dedup tags k_prep left in the workspace).
@@ -46,6 +47,7 @@
 #include "fd_ed25519_pool.h"
 #include "fd_ed25519_tile.h"
 #include "fd_ed25519_strict.h"
+#include "fd_ed25519_gather.h"
 
 /* ------------------------------------------------------------------ */
 /* launch                                                               */
@@ -84,6 +86,18 @@ int
 fd_amd_launch_rebase_off( uint32_t n, uint32_t * d_off, uint32_t const * d_sz, uint32_t lo, hipStream_t stream ) {
   if( !n ) return 0;
   hipLaunchKernelGGL( k_rebase_off, dim3((n + 255u)/256u), dim3(256), 0, stream, n, d_off, d_sz, lo );
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* 4 GATHER_G records per wave and pass, at most `waves` waves (0: no cap) (k_gather, fd_ed25519_gather.h). */
+int
+fd_amd_launch_gather( uint32_t n, fd_amd_gather_rec_t const * d_rec, uint8_t * d_pub, uint8_t * d_sig, uint32_t * d_off,
+                      uint32_t * d_sz, uint8_t * d_blob, uint32_t waves, hipStream_t stream ) {
+  if( !n ) return 0;
+  u32 const per = 4u*GATHER_G;
+  u32 nb = (n + per - 1u)/per;
+  if( waves && nb > waves ) nb = waves;
+  hipLaunchKernelGGL( k_gather, dim3(nb), dim3(64), 0, stream, n, d_rec, d_pub, d_sig, d_off, d_sz, d_blob );
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -160,6 +160,10 @@ def lib():
            "fd_ed25519_amd_multi_verify_txns_tag": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp], i),
            "fd_ed25519_amd_tags_dev": ([ul, vp, vp, vp], i),
            "fd_ed25519_amd_txn_tags_dev": ([ul, vp, vp, vp, vp], i),
+           # pointer-array batches gathered by the GPU from registered memory
+           "fd_ed25519_amd_verify_batch_registered": ([vp, ul, vp, vp, vp, vp, vp], i),
+           "fd_ed25519_amd_verify_batch_registered_tag": ([vp, ul, vp, vp, vp, vp, vp, vp], i),
+           "fd_ed25519_amd_gather_layout": ([ul, vp, ul, ul, vp], ul),
            # debug: k_dsmp's grid, the parked R'
            "fd_ed25519_amd_debug_set_pool_waves": ([ul], None),
            "fd_ed25519_amd_debug_rprime_dev": ([ul, vp, i, vp, vp], i)}
@@ -375,6 +379,42 @@ class Engine:
             raise EngineError("fd_ed25519_amd_verify_batch rc=%d" % rc)
         return (err[:n], tags[:n]) if want_tags else err[:n]
 
+    def verify_batch_ptrs(self, pub_ptr, sig_ptr, msg_ptr, msg_sz, want_tags=False, err=None, tags=None):
+        """fd_ed25519_amd_verify_batch_registered: the pointer-array batch
+        with no host staging.  pub_ptr, sig_ptr, msg_ptr: uint64 arrays of
+        host addresses (32, 64 and msg_sz[i] bytes behind them, any
+        alignment), every range inside one host_register registration; the
+        GPU fetches the bytes itself.  want_tags: (err, tag).  err / tags:
+        preallocated outputs (int8 / uint64, n entries); an EngineError
+        leaves them untouched."""
+        pp = np.ascontiguousarray(pub_ptr, np.uint64)
+        sp = np.ascontiguousarray(sig_ptr, np.uint64)
+        mp = np.ascontiguousarray(msg_ptr, np.uint64)
+        sz = np.ascontiguousarray(msg_sz, np.uint64)
+        n = int(pp.size)
+        assert sp.size == n and mp.size == n and sz.size == n
+        if err is None:
+            err = np.zeros(max(n, 1), np.int8)
+        if want_tags:
+            if tags is None:
+                tags = np.zeros(max(n, 1), np.uint64)
+            rc = lib().fd_ed25519_amd_verify_batch_registered_tag(self._h, n, _ptr(mp), _ptr(sz), _ptr(sp), _ptr(pp),
+                                                                  _ptr(err), _ptr(tags))
+        else:
+            rc = lib().fd_ed25519_amd_verify_batch_registered(self._h, n, _ptr(mp), _ptr(sz), _ptr(sp), _ptr(pp), _ptr(err))
+        if rc:
+            raise EngineError("fd_ed25519_amd_verify_batch_registered rc=%d" % rc)
+        return (err[:n], tags[:n]) if want_tags else err[:n]
+
+    def verify_batch_registered(self, arena, pub_off, sig_off, msg_off, msg_sz, want_tags=False):
+        """verify_batch_ptrs over one registered uint8 arena (host_register):
+        signature i has its key at arena[pub_off[i]], its signature at
+        arena[sig_off[i]] and its message at arena[msg_off[i] : + msg_sz[i]]."""
+        assert arena.dtype == np.uint8 and arena.flags["C_CONTIGUOUS"]
+        base = np.uint64(arena.ctypes.data)
+        return self.verify_batch_ptrs(base + np.asarray(pub_off, np.uint64), base + np.asarray(sig_off, np.uint64),
+                                      base + np.asarray(msg_off, np.uint64), msg_sz, want_tags=want_tags)
+
     def verify_txns(self, payload, txn_off, txn_sz, want_sigs=False, want_tags=False):
         """Wire-format transaction batch (include/fd_txn_amd.h): parse on the
         GPU, verify every signature (multi-signer rule), one verdict per
@@ -425,6 +465,32 @@ def _verify_txns(name, h, payload, txn_off, txn_sz, want_sigs, want_tags=False):
     if want_tags:
         out += (ttag[:n], stag[:int(base[-1])])
     return out if len(out) > 1 else out[0]
+
+
+def gather_layout(sz, cap, blob_cap):
+    """Python mirror of fd_ed25519_amd_gather_layout: how
+    verify_batch_registered sizes one chunk.  Of the message sizes sz the chunk
+    takes the first, always, and further ones while the count stays <= cap and
+    the padded total, the sum of the sizes rounded up to 16, stays <=
+    blob_cap.  Returns (count, dst): dst uint32 (count,), each message's
+    offset in the chunk's blob."""
+    dst, b = [], 0
+    for s in sz:
+        s = int(s)
+        pad = (s + 15) & ~15
+        if dst and (len(dst) >= cap or s > blob_cap or b + pad > blob_cap):
+            break
+        dst.append(b)
+        b += pad
+    return len(dst), np.asarray(dst, np.uint32)
+
+
+def gather_layout_c(sz, cap, blob_cap):
+    """fd_ed25519_amd_gather_layout itself (the library's; no device)."""
+    sz = np.ascontiguousarray(sz, np.uint64)
+    dst = np.zeros(max(sz.size, 1), np.uint32)
+    c = int(lib().fd_ed25519_amd_gather_layout(int(sz.size), _ptr(sz), int(cap), int(blob_cap), _ptr(dst)))
+    return c, dst[:c]
 
 
 def shard_range(n, ndev, r):

@@ -245,6 +245,49 @@ fd_ed25519_amd_verify_soa_registered( fd_ed25519_amd_t * eng,
                                       ulong              blob_sz,
                                       schar *            err );
 
+/* Pointer-array batch from registered memory: the arguments, verdicts and
+   engine mode of fd_ed25519_amd_verify_batch, without its staging.  The
+   host copies no record byte: per chunk it writes one 32-B record per
+   signature (three device addresses, the size, an offset), and a kernel
+   (k_gather) fetches the 32 + 64 + sz bytes over PCIe straight into the
+   device planes the verify kernels read.  pub[i], sig[i] and msg[i] may have
+   any byte alignment, may repeat and may overlap.
+
+   Requirement: every [pub[i], +32), [sig[i], +64) and non-empty
+   [msg[i], +sz[i]) lies inside ONE registration made through
+   fd_ed25519_amd_host_register (its first and its last byte in the same
+   one; two adjacent registrations do not make one range).  Only that table
+   is consulted: memory pinned or registered by other means is refused, as a
+   HIP pointer query per signature would cost more than the copy this call
+   saves.  msg[i] is not looked at when sz[i] is 0.
+
+   Every argument of every signature is checked before anything launches:
+   a NULL array, a NULL pub[i] / sig[i], a NULL msg[i] with sz[i] > 0,
+   sz[i] > blob_max, or a range the table does not hold returns
+   FD_ED25519_AMD_ERR_INVAL with err (and tag) untouched and nothing in
+   flight; the GPU is never given an address the table did not produce.
+   Unregistering memory, or changing the pointer arrays, during the call is
+   the caller's error (as for fd_ed25519_amd_verify_soa_registered).  The
+   _tag form is declared with the other tagged calls below. */
+int
+fd_ed25519_amd_verify_batch_registered( fd_ed25519_amd_t *   eng,
+                                        ulong                n,
+                                        void const * const * msg,
+                                        ulong const *        sz,
+                                        void const * const * sig,
+                                        void const * const * pub,
+                                        schar *              err );
+
+/* How fd_ed25519_amd_verify_batch_registered cuts a batch into chunks (pure
+   host code, no device): of n signatures with message sizes sz[], one chunk
+   takes the first -- always -- and further ones while the count stays <= cap
+   (the engine's batch_max) and the padded total, the sum of
+   round_up( sz[i], 16 ), stays <= blob_cap (its blob_max).  Returns the
+   number taken and writes dst[0 .. that): each message's offset in the
+   chunk's device blob, a multiple of 16, ascending. */
+ulong
+fd_ed25519_amd_gather_layout( ulong n, ulong const * sz, ulong cap, ulong blob_cap, uint * dst );
+
 /* Multi-device engine (SURVEY s8 e: signatures are independent, so a batch
    shards with no exchange step).  One engine and one persistent host thread
    per entry of devices[0..ndev) (a device may be listed more than once:
@@ -342,6 +385,16 @@ fd_ed25519_amd_verify_batch_tag( fd_ed25519_amd_t *   eng,
                                  void const * const * pub,
                                  schar *              err,
                                  ulong *              tag );
+
+int
+fd_ed25519_amd_verify_batch_registered_tag( fd_ed25519_amd_t *   eng,
+                                            ulong                n,
+                                            void const * const * msg,
+                                            ulong const *        sz,
+                                            void const * const * sig,
+                                            void const * const * pub,
+                                            schar *              err,
+                                            ulong *              tag );
 
 int
 fd_ed25519_amd_verify_soa_tag( fd_ed25519_amd_t * eng,
