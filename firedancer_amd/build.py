@@ -75,15 +75,17 @@ def build_engine(force=False, verbose=False, out=None, defines=(), vgpr_guard=Tr
 
     with ThreadPoolExecutor(max_workers=min(len(SOURCES), max(1, min(8, os.cpu_count() or 1)))) as ex:
         list(ex.map(cc, range(len(SOURCES))))
-    n = loop_spill_stores(objs[0], TILE_KERNEL) if vgpr_guard else 0
-    if n is None:   # fail closed: a build whose tile kernel cannot be inspected is not shipped
-        raise RuntimeError("cannot inspect k_tile_persist for in-loop VGPR spills (the LLVM tools under "
-                           "/opt/rocm/lib/llvm/bin are missing, or the kernel symbol %s is not in the code "
-                           "object): refusing the build; see profiles/r05_scout_stop_cause.txt" % TILE_KERNEL)
-    if n:
-        raise RuntimeError("k_tile_persist spills VGPRs to scratch inside its persistent loop (%d scratch stores after "
-                           "the first s_sleep): every such build lost its scout wave on hardware; see "
-                           "profiles/r05_scout_stop_cause.txt" % n)
+    # both instantiations of the persistent loop, the same check: either one spilling in its loop refuses the build
+    for name, kernel in (("k_tile_persist", TILE_KERNEL), ("k_tile_persist_strict", TILE_KERNEL_STRICT)):
+        n = loop_spill_stores(objs[0], kernel) if vgpr_guard else 0
+        if n is None:   # fail closed: a build whose tile kernel cannot be inspected is not shipped
+            raise RuntimeError("cannot inspect %s for in-loop VGPR spills (the LLVM tools under "
+                               "/opt/rocm/lib/llvm/bin are missing, or the kernel symbol %s is not in the code "
+                               "object): refusing the build; see profiles/r05_scout_stop_cause.txt" % (name, kernel))
+        if n:
+            raise RuntimeError("%s spills VGPRs to scratch inside its persistent loop (%d scratch stores after "
+                               "the first s_sleep): every such build lost its scout wave on hardware; see "
+                               "profiles/r05_scout_stop_cause.txt" % (name, n))
     cmd = [_hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib + ".tmp"] + objs + ["-lpthread"]
     if verbose:
         print(" ".join(cmd))
@@ -162,6 +164,8 @@ def kernel_vgprs(obj, kernel):
 # while a 256-VGPR build that spills only in its prologue runs clean,
 # profiles/r05_scout_stop_cause.txt) -- refuse such a build
 TILE_KERNEL = "_Z14k_tile_persist18fd_amd_tile_args_t"
+# the same loop with the strict overlay in every chunk (the tile's FD_ED25519_AMD_MODE_STRICT): the same guard
+TILE_KERNEL_STRICT = "_Z21k_tile_persist_strict18fd_amd_tile_args_t"
 
 
 def build_diag(force=False, verbose=False):

@@ -5,7 +5,9 @@
  * launch after the DSM stage (after k_fin on the pooled path) re-decides
  * every verdict from the raw input bytes, the decompression planes and the
  * R' that the DSM kernel parked in the signature's Ai slab; nothing upstream
- * changes, and the default mode never launches it.
+ * changes, and the default mode never launches it.  The per-signature
+ * decision (strict_decide) is shared with the streaming tile, whose strict
+ * kernel runs it inside each chunk (fd_ed25519_tile.h).
  *
  * The rule, in this order:
  *   1. s = LE(sig[32:64]) >= L                                    -> -1
@@ -85,13 +87,14 @@ strict_point_eq( fe const & X, fe const & Y, fe const & Z, fe const & RX, fe con
   return !fe_isnonzero( dx ) && !fe_isnonzero( dy );
 }
 
-/* One lane per signature.  err holds the reference pipeline's verdicts and
-   receives the strict ones; out (NULL = none; the latency path's mapped
-   host buffer) receives every final verdict, so that in strict mode no
-   reference verdict reaches the host (k_dsm8 / k_dsm4 are then launched
-   with out = NULL).  Untouched: slots with skip[i] != 0 (transaction slots
-   that failed to parse) and slots carrying FD_AMD_VERDICT_DEVICE (k_dsmp's
-   step guard tripped: k_fin marked the whole launch).
+/* The strict verdict of signature slot i from the reference pipeline's
+   verdict `code`: the rule above over the slot's raw bytes (pub + 32 i,
+   sig + 64 i: 32- / 64-byte aligned records, as k_prep reads them), its ds
+   flags and the R' that DSM kernel `kind` (STRICT_*) parked in its Ai slab.
+   The caller leaves alone what the rule does not cover (slots with
+   skip[i] != 0, FD_AMD_VERDICT_DEVICE) and stores the result.  Callers:
+   k_strict below, and the streaming tile's chunk pipeline (tile_chunk<true>,
+   fd_ed25519_tile.h), whose workspace is one wave's N = 64 slice.
 
    Invariant of step 3: a slab is read only for a signature whose DSM ran.
    A verdict of 0 or -3 is written by a DSM compare alone (k_dsm / k_dsm4 /
@@ -100,6 +103,43 @@ strict_point_eq( fe const & X, fe const & Y, fe const & Z, fe const & RX, fe con
    0 without a DSM, and step 1 has turned that into -1 before step 3 looks.
    The ds flags are likewise read only where they were written: k_decomp
    skips signatures k_prep decided, and those are exactly step 1's. */
+FD_DEV int
+strict_decide( u32 i, u8 const * __restrict__ pub, u8 const * __restrict__ sig, int code, u8 const * __restrict__ ws,
+               ws_layout_t L, int kind ) {
+  /* R || s and A as LE dwords */
+  uint4 const * S4 = (uint4 const *)(sig + 64UL*i);
+  uint4 const * P4 = (uint4 const *)(pub + 32UL*i);
+  uint4 const r0 = S4[0], r1 = S4[1], s0 = S4[2], s1 = S4[3], a0 = P4[0], a1 = P4[1];
+  u32 const sw[8] = { s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w };
+  u32 const Lw[8] = { 0x5cf5d3edu, 0x5812631au, 0xa2f79cd6u, 0x14def9deu, 0u, 0u, 0u, 0x10000000u };
+  if( ge256( sw, Lw ) ) return -1;                                                   /* step 1 */
+  if( code == -2 || strict_bad_encoding( a0, a1 ) || strict_bad_encoding( r0, r1 ) ||
+      (ws[L.ds + 2u*i] | ws[L.ds + 2u*i + 1u]) ) return -2;                          /* step 2 */
+  if( code == 0 || code == -3 ) {                                                    /* steps 3, 4 */
+    size_t const N = L.N;
+    i32 const * Ail = (i32 const *)(ws + L.Ai) + (size_t)i*384u;
+    fe X, Y, Z;
+    switch( kind ) {   /* a kernel argument or a chunk's mode: a scalar branch */
+    case STRICT_DSM:  dsm_load_parked ( X, Y, Z, Ail ); break;
+    case STRICT_DSM4: dsm4_load_parked( X, Y, Z, Ail ); break;
+    case STRICT_DSM8: dsm8_load_parked( X, Y, Z, Ail ); break;
+    default:          pool_load_parked( X, Y, Z, Ail, ((int const *)(ws + L.top))[i] ); break;
+    }
+    i32 const * Rw = (i32 const *)(ws + L.R);
+    fe RX, RY;
+    _Pragma("unroll") for( int k=0; k<10; k++ ) { RX.v[k] = Rw[(size_t)k*N + i]; RY.v[k] = Rw[(size_t)(10+k)*N + i]; }
+    code = strict_point_eq( X, Y, Z, RX, RY ) ? 0 : -3;
+  }
+  return code;
+}
+
+/* One lane per signature.  err holds the reference pipeline's verdicts and
+   receives the strict ones; out (NULL = none; the latency path's mapped
+   host buffer) receives every final verdict, so that in strict mode no
+   reference verdict reaches the host (k_dsm8 / k_dsm4 are then launched
+   with out = NULL).  Untouched: slots with skip[i] != 0 (transaction slots
+   that failed to parse) and slots carrying FD_AMD_VERDICT_DEVICE (k_dsmp's
+   step guard tripped: k_fin marked the whole launch). */
 __global__ void __launch_bounds__(64)
 k_strict( u32 n, u8 const * __restrict__ pub, u8 const * __restrict__ sig, i8 * __restrict__ err,
           u8 const * __restrict__ ws, ws_layout_t L, i8 const * __restrict__ skip, int kind, i8 * __restrict__ out ) {
@@ -107,30 +147,7 @@ k_strict( u32 n, u8 const * __restrict__ pub, u8 const * __restrict__ sig, i8 * 
   if( i >= n ) return;
   int code = (int)err[i];
   if( !(skip && skip[i]) && code != FD_AMD_VERDICT_DEVICE ) {
-    /* R || s and A as LE dwords (sig / pub records are 64- / 32-byte aligned, as k_prep reads them) */
-    uint4 const * S4 = (uint4 const *)(sig + 64UL*i);
-    uint4 const * P4 = (uint4 const *)(pub + 32UL*i);
-    uint4 const r0 = S4[0], r1 = S4[1], s0 = S4[2], s1 = S4[3], a0 = P4[0], a1 = P4[1];
-    u32 const sw[8] = { s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w };
-    u32 const Lw[8] = { 0x5cf5d3edu, 0x5812631au, 0xa2f79cd6u, 0x14def9deu, 0u, 0u, 0u, 0x10000000u };
-    if( ge256( sw, Lw ) ) code = -1;                                                   /* step 1 */
-    else if( code == -2 || strict_bad_encoding( a0, a1 ) || strict_bad_encoding( r0, r1 ) ||
-             (ws[L.ds + 2u*i] | ws[L.ds + 2u*i + 1u]) ) code = -2;                     /* step 2 */
-    else if( code == 0 || code == -3 ) {                                               /* steps 3, 4 */
-      size_t const N = L.N;
-      i32 const * Ail = (i32 const *)(ws + L.Ai) + (size_t)i*384u;
-      fe X, Y, Z;
-      switch( kind ) {   /* a kernel argument: a scalar branch */
-      case STRICT_DSM:  dsm_load_parked ( X, Y, Z, Ail ); break;
-      case STRICT_DSM4: dsm4_load_parked( X, Y, Z, Ail ); break;
-      case STRICT_DSM8: dsm8_load_parked( X, Y, Z, Ail ); break;
-      default:          pool_load_parked( X, Y, Z, Ail, ((int const *)(ws + L.top))[i] ); break;
-      }
-      i32 const * Rw = (i32 const *)(ws + L.R);
-      fe RX, RY;
-      _Pragma("unroll") for( int k=0; k<10; k++ ) { RX.v[k] = Rw[(size_t)k*N + i]; RY.v[k] = Rw[(size_t)(10+k)*N + i]; }
-      code = strict_point_eq( X, Y, Z, RX, RY ) ? 0 : -3;
-    }
+    code = strict_decide( i, pub, sig, code, ws, L, kind );
     err[i] = (i8)code;
   }
   if( out ) out[i] = (i8)code;

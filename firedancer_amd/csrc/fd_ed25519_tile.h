@@ -1,9 +1,11 @@
 /* firedancer_amd/csrc/fd_ed25519_tile.h
  *
  * The streaming tile's persistent kernel (scout, gather, transaction
- * layout, tile_chunk, k_tile_persist), k_tile_synth and their two launch
- * functions.  It runs the bodies of the front and of all three DSM headers;
- * only fd_ed25519_kernels.hip includes it.
+ * layout, tile_chunk, k_tile_persist and its strict instantiation
+ * k_tile_persist_strict), k_tile_synth and their two launch functions.  It
+ * runs the bodies of the front and of all three DSM headers, and in strict
+ * mode fd_ed25519_strict.h's decision; only fd_ed25519_kernels.hip includes
+ * it.
  */
 
 #ifndef FD_ED25519_TILE_H
@@ -14,6 +16,7 @@
 #include "fd_ed25519_dsm4.h"
 #include "fd_ed25519_dsm8.h"
 #include "fd_txn_dev.h"
+#include "fd_ed25519_strict.h"
 
 /* ------------------------------------------------------------------ */
 /* k_tile_persist: the streaming tile's persistent consumer.
@@ -249,9 +252,12 @@ tile_gather( fd_amd_tile_args_t const & A, u32 k, u32 l, u32 e_src, u32 e_out, u
    8 lanes (k_dsm8's body) or 4 lanes (k_dsm4's body); the host keeps a
    chunk's slots within the mode's 64 / 8 / 16 lanes).  PUB_SIG_MSG: entry q is signature slot q.  TXN
    (A.txn): entry q is a wire transaction whose slots tile_txn_layout lays
-   out, and its result is the transaction's verdict. */
+   out, and its result is the transaction's verdict.  STRICT: the strict
+   RFC 8032 verdicts (k_strict's rule, fd_ed25519_strict.h) instead of the
+   reference's; tile_chunk<false> holds no trace of that step. */
+template<bool STRICT>
 __device__ __forceinline__ void
-tile_chunk( fd_amd_tile_args_t const & A, u64 c0, u32 k, u32 mode, u8 * __restrict__ scr, ws_layout_t L,
+tile_chunk(fd_amd_tile_args_t const & A, u64 c0, u32 k, u32 mode, u8 * __restrict__ scr, ws_layout_t L,
             tile_scratch_t const & S, i32 (* __restrict__ bi)[48], u64 (* __restrict__ evl)[33], u64 * pt, u64 tc,
             u32 pp = 0u ) {
   /* pp = pair | pair_seq << 2 (quad pairs, FD_AMD_TILE_PAIR); pair: 0 none;
@@ -320,6 +326,22 @@ tile_chunk( fd_amd_tile_args_t const & A, u64 c0, u32 k, u32 mode, u8 * __restri
   else                               dsm_lane_body( l, n, err, ws, L, 0, bi, evl, tc );
   __builtin_amdgcn_s_setprio( 0 );
   __syncthreads();
+  if constexpr( STRICT ) {
+    /* the strict overlay, one lane per signature slot, over the slots whose
+       DSM this wave ran (a pair's sub 1: [16, k) = dsm4_body's g0 >> 2 on),
+       from the parked layout of the chunk's mode.  strict_decide's invariant
+       holds as in k_strict: prep_body, decomp_body and the DSM body above
+       are the batch kernels' bodies.  A slot whose transaction failed to
+       parse keeps its skip.  No wait and no loop over memory: the chunk's
+       own scratch, written before the barrier above.  Every lane reaches
+       the barrier below; the result stores then read err[] as ever. */
+    u32 const si = (g0 >> 2) + l;
+    if( si < nd && !(txn && skp[si]) ) {
+      int const kind = mode == TILE_MODE_LAT8 ? STRICT_DSM8 : mode == TILE_MODE_QUAD4 ? STRICT_DSM4 : STRICT_DSM;
+      err[si] = (i8)strict_decide( si, pub, sig, (int)err[si], ws, L, kind );
+    }
+    __syncthreads();
+  }
   TILE_STAMP( 2 );
   /* 4. results: tags (and, zero-copy, the output frames above) first, one
         system-scope release, then the words the host polls.  TXN: an entry's
@@ -349,107 +371,117 @@ tile_chunk( fd_amd_tile_args_t const & A, u64 c0, u32 k, u32 mode, u8 * __restri
 # undef TILE_STAMP
 }
 
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
-k_tile_persist( fd_amd_tile_args_t A ) {
-  constexpr ws_layout_t    L = ws_layout_const( 64 );   /* every plane offset an immediate */
-  constexpr tile_scratch_t S = tile_scratch_layout();
-  __shared__ __attribute__((aligned(16))) i32 bi[8][48];
-  __shared__ u64 evl[64][33];
-  fd_amd_tile_dctl_t * D = A.dctl;
-  u32 const l = threadIdx.x;
-  if( blockIdx.x == 0u ) {
-    if( l == 0u ) tile_scout( D, A.hctl, A.watchdog );
-    return;
-  }
-  bi12_fill( bi );
-  __syncthreads();
-  /* this wave's mirror word: its XCD's (HW_REG_XCC_ID) */
-  u32 const xcc = __builtin_amdgcn_s_getreg( 20 | (0 << 6) | (3 << 11) ) % FD_AMD_TILE_MIRRORS;
-  u64 const * mw = &D->mw[xcc].w;
-  u8 * scr = A.scratch + (size_t)blockIdx.x * S.total;
-  /* per-wave tallies in LDS, not registers (the DSM bodies want every VGPR):
-     [0..7] diagnostics build (A.prof) gather, front, DSM, results, wait,
-     fence, -, -; [8..13] dctl->stat: latency chunks, throughput chunks,
-     their frags, quad chunks, their frags */
-  __shared__ u64 s_tally[16];
-  if( l < 16u ) s_tally[l] = 0UL;
-  u64 * const pt = s_tally;
-  /* A run-time flag (the host sets it only in the diagnostics build), not a
-     compile-time constant: with the profiling branches folded away the
-     compiler gives this kernel all 256 VGPRs, and at 256 its scout wave
-     stopped ~0.7 ms into every run, called or inlined (profiles/
-     r04_tile_scout_vgpr_ab.txt, r05_scout_stop_cause.txt); build.py refuses
-     a build at 256. */
-  bool const prof = A.prof != 0u;
-  for( ;; ) {
-    u64 t = 0;
-    if( l == 0u ) t = atomicAdd( (unsigned long long *)&D->ticket, 1ULL );
-    t = rfl64( t );
-    /* wait for descriptor t: poll the mirror, backing off with the
-       distance to the head (the next in line polls every ~0.2 us) */
-    u64 t0 = __builtin_amdgcn_s_memrealtime(), tw = t0, last = ~0UL;
-    bool go = false;
-    for( ;; ) {
-      u64 const w = rfl64( l == 0u ? ld_dev64( mw ) : 0UL );
-      if( TILE_MW_HEAD( w ) > t ) { go = true; break; }
-      if( w & (TILE_MW_ERR | TILE_MW_STOP) ) break;
-      u64 const now = __builtin_amdgcn_s_memrealtime();
-      if( w != last ) { last = w; tw = now; }
-      else if( now - tw > A.watchdog ) break;       /* no scout (or host) for that long: give up */
-      u64 const d = t - TILE_MW_HEAD( w );
-      u32 const nap = d < 2UL ? 1u : d < 64UL ? (u32)d : 64u;
-      for( u32 z = 0; z < nap; z++ ) __builtin_amdgcn_s_sleep( 4 );
-    }
-    if( prof && !l ) pt[4] += __builtin_amdgcn_s_memrealtime() - t0;
-    if( !go ) break;
-    u64 const tc = __builtin_amdgcn_s_memrealtime();   /* claimed */
-    /* descriptor t (host memory): { first ring index, count | FD_AMD_TILE_LAT | FD_AMD_TILE_QUAD } */
-    u64 c = 0, cm = 0;
-    if( l == 0u ) {
-      u64 const * dp = (u64 const *)(A.desc + (t & A.mask));
-      c = ld_sys64( dp ); cm = ld_sys64( dp + 1 );
-    }
-    c = rfl64( c ); cm = rfl64( cm );
-    u32 const take = FD_AMD_TILE_COUNT( (u32)cm );
-    u32 const md = ((u32)cm & FD_AMD_TILE_LAT) ? TILE_MODE_LAT8 : ((u32)cm & FD_AMD_TILE_QUAD) ? TILE_MODE_QUAD4 : TILE_MODE_THR;
-    /* quad pair: its shared workspace and flag; sub 1 first waits for sub 0's front */
-    u32 const pr = ((u32)cm & FD_AMD_TILE_PAIR) && A.pair_ws && !A.txn && md == TILE_MODE_QUAD4 ? 1u + (u32)((cm >> 32) & 1UL) : 0u;
-    u32 const pseq = (u32)(cm >> 33) & 0x3fffffffu;
-    u8 * cscr = pr ? A.pair_ws + (size_t)(pseq & A.pair_mask) * S.total : scr;
-    u32 * pf = pr ? A.pair_flag + (pseq & A.pair_mask) : (u32 *)0;
-    bool pok = true;
-    if( pr == 2u ) {
-      u64 const tp = __builtin_amdgcn_s_memrealtime();
-      for( ;; ) {
-        u32 const f = (u32)__builtin_amdgcn_readfirstlane( (int)(l == 0u ? ld_dev32( pf ) : 0u) );
-        if( f == pseq + 1u ) break;
-        u64 const w = rfl64( l == 0u ? ld_dev64( mw ) : 0UL );
-        if( (w & TILE_MW_ERR) || __builtin_amdgcn_s_memrealtime() - tp > A.watchdog ) { pok = false; break; }
-        __builtin_amdgcn_s_sleep( 2 );
-      }
-      __builtin_amdgcn_fence( __ATOMIC_ACQUIRE, "agent" );   /* sub 0's workspace writes (another XCD's L2) */
-    }
-    /* the frames were written by the host (copy mode) or the producer
-       (zero-copy) into host memory: drop this CU's stale lines first */
-    u64 const tf = prof ? __builtin_amdgcn_s_memrealtime() : 0UL;
-    __builtin_amdgcn_fence( __ATOMIC_ACQUIRE, "" );
-    asm volatile( "s_waitcnt vmcnt(0)" ::: "memory" );
-    if( prof && !l ) pt[5] += __builtin_amdgcn_s_memrealtime() - tf;
-    if( take && take <= 64u && pok && (!pr || (take > 16u && take <= 32u)) )
-      tile_chunk( A, c, take, md, cscr, L, S, bi, evl, pt, tc, pr | pseq << 2 );
-    if( !l ) {
-      /* dctl->stat slots: chunks, frags -- latency 0, 2; throughput 1, 3; quad 4, 5 (a pair sub is a quad chunk) */
-      u32 const tc_ = md == TILE_MODE_LAT8 ? 0u : md == TILE_MODE_THR ? 1u : 4u;
-      u32 const tf_ = md == TILE_MODE_LAT8 ? 2u : md == TILE_MODE_THR ? 3u : 5u;
-      s_tally[8u + tc_] += 1UL; s_tally[8u + tf_] += pr == 1u ? 16u : pr == 2u ? take - 16u : take;
-      atomicAdd( (unsigned long long *)&D->done, 1ULL );   /* progress, mirrored to the host by the scout */
-    }
-  }
-  if( l == 0u ) {
-    _Pragma("unroll") for( int q=0; q<6; q++ ) atomicAdd( (unsigned long long *)&D->stat[q], (unsigned long long)s_tally[8 + q] );
-    if( prof ) { _Pragma("unroll") for( int q=0; q<8; q++ ) atomicAdd( (unsigned long long *)&D->prof[q], (unsigned long long)pt[q] ); }
-  }
+/* The persistent kernel's text, once per verdict mode: NAME_ runs
+   tile_chunk<STRICT_>.  A macro and not a shared inline body: with the loop
+   in a forceinline template called by two thin kernels the reference
+   kernel's code changed (3 more SGPR spills, 60 more instructions), while
+   two expansions of the same text leave k_tile_persist's instructions as
+   they were before the strict kernel existed. */
+#define TILE_PERSIST_KERNEL( NAME_, STRICT_ )                                                                                            \
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))                                                            \
+NAME_( fd_amd_tile_args_t A ) {                                                                                                          \
+  constexpr ws_layout_t    L = ws_layout_const( 64 );   /* every plane offset an immediate */                                            \
+  constexpr tile_scratch_t S = tile_scratch_layout();                                                                                    \
+  __shared__ __attribute__((aligned(16))) i32 bi[8][48];                                                                                 \
+  __shared__ u64 evl[64][33];                                                                                                            \
+  fd_amd_tile_dctl_t * D = A.dctl;                                                                                                       \
+  u32 const l = threadIdx.x;                                                                                                             \
+  if( blockIdx.x == 0u ) {                                                                                                               \
+    if( l == 0u ) tile_scout( D, A.hctl, A.watchdog );                                                                                   \
+    return;                                                                                                                              \
+  }                                                                                                                                      \
+  bi12_fill( bi );                                                                                                                       \
+  __syncthreads();                                                                                                                       \
+  /* this wave's mirror word: its XCD's (HW_REG_XCC_ID) */                                                                               \
+  u32 const xcc = __builtin_amdgcn_s_getreg( 20 | (0 << 6) | (3 << 11) ) % FD_AMD_TILE_MIRRORS;                                          \
+  u64 const * mw = &D->mw[xcc].w;                                                                                                        \
+  u8 * scr = A.scratch + (size_t)blockIdx.x * S.total;                                                                                   \
+  /* per-wave tallies in LDS, not registers (the DSM bodies want every VGPR):                                                            \
+     [0..7] diagnostics build (A.prof) gather, front, DSM, results, wait,                                                                \
+     fence, -, -; [8..13] dctl->stat: latency chunks, throughput chunks,                                                                 \
+     their frags, quad chunks, their frags */                                                                                            \
+  __shared__ u64 s_tally[16];                                                                                                            \
+  if( l < 16u ) s_tally[l] = 0UL;                                                                                                        \
+  u64 * const pt = s_tally;                                                                                                              \
+  /* A run-time flag (the host sets it only in the diagnostics build), not a                                                             \
+     compile-time constant: with the profiling branches folded away the                                                                  \
+     compiler gives this kernel all 256 VGPRs, and at 256 its scout wave                                                                 \
+     stopped ~0.7 ms into every run, called or inlined (profiles/                                                                        \
+     r04_tile_scout_vgpr_ab.txt, r05_scout_stop_cause.txt); build.py refuses                                                             \
+     a build at 256. */                                                                                                                  \
+  bool const prof = A.prof != 0u;                                                                                                        \
+  for( ;; ) {                                                                                                                            \
+    u64 t = 0;                                                                                                                           \
+    if( l == 0u ) t = atomicAdd( (unsigned long long *)&D->ticket, 1ULL );                                                               \
+    t = rfl64( t );                                                                                                                      \
+    /* wait for descriptor t: poll the mirror, backing off with the                                                                      \
+       distance to the head (the next in line polls every ~0.2 us) */                                                                    \
+    u64 t0 = __builtin_amdgcn_s_memrealtime(), tw = t0, last = ~0UL;                                                                     \
+    bool go = false;                                                                                                                     \
+    for( ;; ) {                                                                                                                          \
+      u64 const w = rfl64( l == 0u ? ld_dev64( mw ) : 0UL );                                                                             \
+      if( TILE_MW_HEAD( w ) > t ) { go = true; break; }                                                                                  \
+      if( w & (TILE_MW_ERR | TILE_MW_STOP) ) break;                                                                                      \
+      u64 const now = __builtin_amdgcn_s_memrealtime();                                                                                  \
+      if( w != last ) { last = w; tw = now; }                                                                                            \
+      else if( now - tw > A.watchdog ) break;       /* no scout (or host) for that long: give up */                                      \
+      u64 const d = t - TILE_MW_HEAD( w );                                                                                               \
+      u32 const nap = d < 2UL ? 1u : d < 64UL ? (u32)d : 64u;                                                                            \
+      for( u32 z = 0; z < nap; z++ ) __builtin_amdgcn_s_sleep( 4 );                                                                      \
+    }                                                                                                                                    \
+    if( prof && !l ) pt[4] += __builtin_amdgcn_s_memrealtime() - t0;                                                                     \
+    if( !go ) break;                                                                                                                     \
+    u64 const tc = __builtin_amdgcn_s_memrealtime();   /* claimed */                                                                     \
+    /* descriptor t (host memory): { first ring index, count | FD_AMD_TILE_LAT | FD_AMD_TILE_QUAD } */                                   \
+    u64 c = 0, cm = 0;                                                                                                                   \
+    if( l == 0u ) {                                                                                                                      \
+      u64 const * dp = (u64 const *)(A.desc + (t & A.mask));                                                                             \
+      c = ld_sys64( dp ); cm = ld_sys64( dp + 1 );                                                                                       \
+    }                                                                                                                                    \
+    c = rfl64( c ); cm = rfl64( cm );                                                                                                    \
+    u32 const take = FD_AMD_TILE_COUNT( (u32)cm );                                                                                       \
+    u32 const md = ((u32)cm & FD_AMD_TILE_LAT) ? TILE_MODE_LAT8 : ((u32)cm & FD_AMD_TILE_QUAD) ? TILE_MODE_QUAD4 : TILE_MODE_THR;        \
+    /* quad pair: its shared workspace and flag; sub 1 first waits for sub 0's front */                                                  \
+    u32 const pr = ((u32)cm & FD_AMD_TILE_PAIR) && A.pair_ws && !A.txn && md == TILE_MODE_QUAD4 ? 1u + (u32)((cm >> 32) & 1UL) : 0u;     \
+    u32 const pseq = (u32)(cm >> 33) & 0x3fffffffu;                                                                                      \
+    u8 * cscr = pr ? A.pair_ws + (size_t)(pseq & A.pair_mask) * S.total : scr;                                                           \
+    u32 * pf = pr ? A.pair_flag + (pseq & A.pair_mask) : (u32 *)0;                                                                       \
+    bool pok = true;                                                                                                                     \
+    if( pr == 2u ) {                                                                                                                     \
+      u64 const tp = __builtin_amdgcn_s_memrealtime();                                                                                   \
+      for( ;; ) {                                                                                                                        \
+        u32 const f = (u32)__builtin_amdgcn_readfirstlane( (int)(l == 0u ? ld_dev32( pf ) : 0u) );                                       \
+        if( f == pseq + 1u ) break;                                                                                                      \
+        u64 const w = rfl64( l == 0u ? ld_dev64( mw ) : 0UL );                                                                           \
+        if( (w & TILE_MW_ERR) || __builtin_amdgcn_s_memrealtime() - tp > A.watchdog ) { pok = false; break; }                            \
+        __builtin_amdgcn_s_sleep( 2 );                                                                                                   \
+      }                                                                                                                                  \
+      __builtin_amdgcn_fence( __ATOMIC_ACQUIRE, "agent" );   /* sub 0's workspace writes (another XCD's L2) */                           \
+    }                                                                                                                                    \
+    /* the frames were written by the host (copy mode) or the producer                                                                   \
+       (zero-copy) into host memory: drop this CU's stale lines first */                                                                 \
+    u64 const tf = prof ? __builtin_amdgcn_s_memrealtime() : 0UL;                                                                        \
+    __builtin_amdgcn_fence( __ATOMIC_ACQUIRE, "" );                                                                                      \
+    asm volatile( "s_waitcnt vmcnt(0)" ::: "memory" );                                                                                   \
+    if( prof && !l ) pt[5] += __builtin_amdgcn_s_memrealtime() - tf;                                                                     \
+    if( take && take <= 64u && pok && (!pr || (take > 16u && take <= 32u)) )                                                             \
+      tile_chunk<STRICT_>( A, c, take, md, cscr, L, S, bi, evl, pt, tc, pr | pseq << 2 );                                                \
+    if( !l ) {                                                                                                                           \
+      /* dctl->stat slots: chunks, frags -- latency 0, 2; throughput 1, 3; quad 4, 5 (a pair sub is a quad chunk) */                     \
+      u32 const tc_ = md == TILE_MODE_LAT8 ? 0u : md == TILE_MODE_THR ? 1u : 4u;                                                         \
+      u32 const tf_ = md == TILE_MODE_LAT8 ? 2u : md == TILE_MODE_THR ? 3u : 5u;                                                         \
+      s_tally[8u + tc_] += 1UL; s_tally[8u + tf_] += pr == 1u ? 16u : pr == 2u ? take - 16u : take;                                      \
+      atomicAdd( (unsigned long long *)&D->done, 1ULL );   /* progress, mirrored to the host by the scout */                             \
+    }                                                                                                                                    \
+  }                                                                                                                                      \
+  if( l == 0u ) {                                                                                                                        \
+    _Pragma("unroll") for( int q=0; q<6; q++ ) atomicAdd( (unsigned long long *)&D->stat[q], (unsigned long long)s_tally[8 + q] );       \
+    if( prof ) { _Pragma("unroll") for( int q=0; q<8; q++ ) atomicAdd( (unsigned long long *)&D->prof[q], (unsigned long long)pt[q] ); } \
+  }                                                                                                                                      \
 }
+
+TILE_PERSIST_KERNEL( k_tile_persist, false )          /* FD_ED25519_AMD_MODE_REFERENCE */
+TILE_PERSIST_KERNEL( k_tile_persist_strict, true )    /* FD_ED25519_AMD_MODE_STRICT: the same loop, strict overlay per chunk */
 
 #ifdef FD_AMD_DIAG
 /* Diagnostics build only.  Measurement aid: k_tile_persist's chunk pipeline without the host
@@ -486,7 +518,7 @@ k_tile_synth( fd_amd_tile_args_t A, u32 iters, u32 eight ) {
   }
   u8 * scr = A.scratch + (size_t)blockIdx.x * S.total;
   for( u32 it = 0; it < iters; it++ )
-    tile_chunk( A, ((u64)blockIdx.x * iters + it) * k, k, md, scr, L, S, bi, evl, pt, 0UL );
+    tile_chunk<false>( A, ((u64)blockIdx.x * iters + it) * k, k, md, scr, L, S, bi, evl, pt, 0UL );
   if( A.prof && threadIdx.x == 0u ) {
     _Pragma("unroll") for( int q=0; q<8; q++ ) atomicAdd( (unsigned long long *)&A.dctl->prof[q], (unsigned long long)pt[q] );
   }
@@ -501,11 +533,14 @@ fd_amd_launch_tile_synth( fd_amd_tile_args_t const * a, uint32_t waves, uint32_t
 }
 #endif /* FD_AMD_DIAG */
 
+/* strict: nonzero launches k_tile_persist_strict (the run's verdict mode is
+   the choice of kernel, not a field k_tile_persist would read) */
 int
-fd_amd_launch_tile_persist( fd_amd_tile_args_t const * a, uint32_t waves, hipStream_t stream ) {
+fd_amd_launch_tile_persist( fd_amd_tile_args_t const * a, uint32_t waves, hipStream_t stream, int strict ) {
   if( waves < 2u ) return -1;
   (void)hipGetLastError();   /* the check below is the launch's own: every earlier call checked its return code */
-  hipLaunchKernelGGL( k_tile_persist, dim3(waves), dim3(64), 0, stream, *a );
+  if( strict ) hipLaunchKernelGGL( k_tile_persist_strict, dim3(waves), dim3(64), 0, stream, *a );
+  else         hipLaunchKernelGGL( k_tile_persist,        dim3(waves), dim3(64), 0, stream, *a );
   hipError_t const e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;   /* the HIP error, for the caller's message */
 }

@@ -326,6 +326,7 @@ struct fd_verify_amd_tile {
   ulong              batch_max;
   tcache_t           tc;
   int                framing;   /* FD_VERIFY_AMD_FRAMING_* */
+  int                verdict_mode;   /* FD_ED25519_AMD_MODE_*: which kernel the next run launches */
   int                cus;
   uint8_t *          reg_base;  /* host data region mapped into the GPU (zero copy) */
   ulong              reg_sz;
@@ -472,6 +473,22 @@ fd_verify_amd_tile_set_framing( fd_verify_amd_tile_t * t, int framing ) {
   if( framing == FD_VERIFY_AMD_FRAMING_TXN && t->batch_max < TXN_SIG_MAX_AT_MTU ) return FD_ED25519_AMD_ERR_INVAL;
   t->framing = framing;
   return FD_ED25519_AMD_OK;
+}
+
+/* The verdict mode picks the run's kernel (k_tile_persist or
+   k_tile_persist_strict) at its launch; the host side reads the verdict
+   word either kernel stores, so publishing, SV_FILT and the verdict log
+   follow the mode without a branch of their own. */
+extern "C" int
+fd_verify_amd_tile_set_verdict_mode( fd_verify_amd_tile_t * t, int mode ) {
+  if( !t || (mode != FD_ED25519_AMD_MODE_REFERENCE && mode != FD_ED25519_AMD_MODE_STRICT) ) return FD_ED25519_AMD_ERR_INVAL;
+  t->verdict_mode = mode;
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" int
+fd_verify_amd_tile_verdict_mode( fd_verify_amd_tile_t const * t ) {
+  return t ? t->verdict_mode : FD_ED25519_AMD_ERR_INVAL;
 }
 
 extern "C" void *
@@ -683,6 +700,7 @@ fd_verify_amd_tile_new_cfg( fd_verify_amd_tile_cfg_t const * cfg ) {
   fd_verify_amd_tile_t * t = new fd_verify_amd_tile_t();
   t->cfg = c; t->device = c.device; t->batch_max = c.batch_max;
   t->framing = c.framing; t->cus = cus;
+  t->verdict_mode = FD_ED25519_AMD_MODE_REFERENCE;
   t->tc.init( c.tcache_depth );
   bool ok = hipHostMalloc( (void **)&t->out_base, c.out_frame_cnt * FD_VERIFY_AMD_FRAME_SZ, hipHostMallocMapped ) == hipSuccess &&
             hipHostGetDevicePointer( (void **)&t->out_dev, t->out_base, 0 ) == hipSuccess;
@@ -1023,7 +1041,7 @@ tile_run_persist( fd_verify_amd_tile_t * t, fd_frag_meta_t const * in_mcache, ul
 #ifdef FD_AMD_DIAG
   { char const * e = getenv( "FD_AMD_TILE_PROF" ); A.prof = e && *e && *e != '0'; }   /* diagnostics build only */
 #endif
-  int const lrc = fd_amd_launch_tile_persist( &A, t->waves, t->pst );
+  int const lrc = fd_amd_launch_tile_persist( &A, t->waves, t->pst, t->verdict_mode == FD_ED25519_AMD_MODE_STRICT );
   if( lrc || hipEventRecord( t->pdone, t->pst ) != hipSuccess ) {
     fprintf( stderr, "fd_verify_amd_tile_run: launching the tile kernel failed (%d: %s; %u waves)\n", lrc,
              lrc > 0 ? hipGetErrorString( (hipError_t)lrc ) : "-", (unsigned)t->waves );
@@ -1831,7 +1849,8 @@ fd_verify_amd_bench_stream( int device, ulong batch_max, ulong batch_wait_ns, do
   copier_stall_ns.store( (flags & FD_VERIFY_AMD_BENCH_STALL_HELPER) ? 200000UL : 0UL, std::memory_order_relaxed );
   fd_verify_amd_tile_t * tile = fd_verify_amd_tile_new_cfg( &cfg );
   if( !tile ) { free( dcache ); return FD_ED25519_AMD_ERR_DEVICE; }
-  if( zero_copy && fd_verify_amd_tile_register_dcache( tile, dcache, region ) ) {
+  if( flags & FD_VERIFY_AMD_BENCH_STRICT ) (void)fd_verify_amd_tile_set_verdict_mode( tile, FD_ED25519_AMD_MODE_STRICT );
+  if( zero_copy&& fd_verify_amd_tile_register_dcache( tile, dcache, region ) ) {
     fd_verify_amd_tile_delete( tile ); free( dcache ); return FD_ED25519_AMD_ERR_DEVICE;
   }
   uchar const * out_chunk0 = (uchar const *)fd_verify_amd_tile_out_chunk0( tile );

@@ -164,6 +164,8 @@ def lib():
            "fd_ed25519_amd_verify_batch_registered": ([vp, ul, vp, vp, vp, vp, vp], i),
            "fd_ed25519_amd_verify_batch_registered_tag": ([vp, ul, vp, vp, vp, vp, vp, vp], i),
            "fd_ed25519_amd_gather_layout": ([ul, vp, ul, ul, vp], ul),
+           # the streaming tile's verdict mode
+           "fd_verify_amd_tile_set_verdict_mode": ([vp, i], i), "fd_verify_amd_tile_verdict_mode": ([vp], i),
            # debug: k_dsmp's grid, the parked R'
            "fd_ed25519_amd_debug_set_pool_waves": ([ul], None),
            "fd_ed25519_amd_debug_rprime_dev": ([ul, vp, i, vp, vp], i)}

@@ -92,9 +92,10 @@ class VerifyTile:
     FRAME_SZ = 1408
 
     def __init__(self, device=0, batch_max=4096, batch_wait_ns=0, tcache_depth=1 << 16, framing=0, out_frame_cnt=0,
-                 **cfg):
-        """cfg: further fd_verify_amd_tile_cfg_t fields (waves, chunk_mode, publish_cpu, window, lat_fill_ns,
-        lat_free_chunks, chunk_wait_ns, thr_rate_hi, thr_rate_lo, halt_grace_ns, copy_cpu)."""
+                 mode=ed25519.MODE_REFERENCE, **cfg):
+        """mode: ed25519.MODE_REFERENCE (default) or MODE_STRICT, the verdicts of the tile's runs
+        (set_verdict_mode).  cfg: further fd_verify_amd_tile_cfg_t fields (waves, chunk_mode, publish_cpu,
+        window, lat_fill_ns, lat_free_chunks, chunk_wait_ns, thr_rate_hi, thr_rate_lo, halt_grace_ns, copy_cpu)."""
         L = ed25519.lib()
         self._h = None
         c = TileCfg.default(device=int(device), batch_max=int(batch_max), batch_wait_ns=int(batch_wait_ns),
@@ -107,6 +108,24 @@ class VerifyTile:
         base = L.fd_verify_amd_tile_out_chunk0(self._h)
         nbytes = int(L.fd_verify_amd_tile_out_data_sz(self._h))
         self.out_region = np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(base))
+        if mode != ed25519.MODE_REFERENCE:
+            try:
+                self.set_verdict_mode(mode)
+            except Exception:
+                self.close()
+                raise
+
+    def set_verdict_mode(self, mode):
+        """fd_verify_amd_tile_set_verdict_mode: ed25519.MODE_REFERENCE or MODE_STRICT for the runs that
+        follow (between runs; a bad mode raises and leaves the mode as it was)."""
+        rc = ed25519.lib().fd_verify_amd_tile_set_verdict_mode(self._h, int(mode))
+        if rc:
+            raise ed25519.EngineError("fd_verify_amd_tile_set_verdict_mode(%r) rc=%d" % (mode, rc))
+
+    @property
+    def verdict_mode(self):
+        """The verdict mode of the next run (ed25519.MODE_*)."""
+        return int(ed25519.lib().fd_verify_amd_tile_verdict_mode(self._h))
 
     def close(self):
         if self._h:
@@ -171,16 +190,17 @@ class VerifyTile:
 
 BENCH_ZERO_COPY, BENCH_WRITE, BENCH_LAP, BENCH_SAMPLE_BYTES = 1, 2, 4, 8
 BENCH_CHUNK_LAT, BENCH_CHUNK_THR, BENCH_PUB_INLINE, BENCH_TXN, BENCH_COPY_INLINE = 16, 32, 64, 128, 256
-BENCH_STALL_HELPER, BENCH_CHUNK_QUAD = 512, 1024
+BENCH_STALL_HELPER, BENCH_CHUNK_QUAD, BENCH_STRICT = 512, 1024, 2048
 
 
 def bench_stream(device, batch_max, batch_wait_ns, pub, sig, msg_off, msg_sz, blob, frag_cnt, rate=0.0,
                  zero_copy=False, writes=False, lap=False, dcache_frames=0, expect_err=None, expect_tag=None,
                  sample_bytes=False, chunk_mode=0, pub_inline=False, txn=False, waves=0, copy_inline=False,
-                 stall_helper=False):
+                 stall_helper=False, strict=False):
     """fd_verify_amd_bench_stream: producer (rate frags/s, 0 = saturate) -> tile -> consumer; returns
     dict(frags_per_s, p50_ns, p99_ns, p999_ns, mean_batch, published, sv_filt, ovrn, mismatches, checked).
-    With expect_err/expect_tag (per pool entry) the consumer checks every published frag."""
+    With expect_err/expect_tag (per pool entry) the consumer checks every published frag.  strict: the tile
+    runs in ed25519.MODE_STRICT, and expect_err holds the strict verdicts."""
     out = (ctypes.c_double * 49)()
     p = [np.ascontiguousarray(a) for a in (pub, sig, msg_off, msg_sz, blob)]
     ee = np.ascontiguousarray(expect_err, np.int8) if expect_err is not None else None
@@ -188,7 +208,7 @@ def bench_stream(device, batch_max, batch_wait_ns, pub, sig, msg_off, msg_sz, bl
     flags = (BENCH_ZERO_COPY if zero_copy else 0) | (BENCH_WRITE if writes else 0) | (BENCH_LAP if lap else 0) | \
         (BENCH_SAMPLE_BYTES if sample_bytes else 0) | {0: 0, 1: BENCH_CHUNK_LAT, 2: BENCH_CHUNK_THR, 3: BENCH_CHUNK_QUAD}[chunk_mode] | \
         (BENCH_PUB_INLINE if pub_inline else 0) | (BENCH_TXN if txn else 0) | (BENCH_COPY_INLINE if copy_inline else 0) | \
-        (BENCH_STALL_HELPER if stall_helper else 0)
+        (BENCH_STALL_HELPER if stall_helper else 0) | (BENCH_STRICT if strict else 0)
     vp = ctypes.c_void_p
     rc = ed25519.lib().fd_verify_amd_bench_stream(int(device), int(batch_max), int(batch_wait_ns), float(rate), flags,
                                                   int(dcache_frames), p[2].shape[0],

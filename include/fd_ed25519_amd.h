@@ -172,9 +172,11 @@ fd_ed25519_amd_delete( fd_ed25519_amd_t * eng );
    point of the engine (verify_batch, verify_soa, verify_soa_registered,
    verify_txns and the multi-engine forms); the workspace footprint is the
    same.  It costs one more small kernel per batch (measured in
-   profiles/strict_cost.json).  Not covered: the drop-in fd_ed25519_verify
-   (the reference's API keeps the reference's verdicts) and the streaming
-   verify tile (include/fd_tango_amd.h), which always run in reference mode.
+   profiles/strict_cost.json).  The streaming verify tile has a verdict
+   mode of its own with the same rule (fd_verify_amd_tile_set_verdict_mode,
+   include/fd_tango_amd.h; cost in profiles/tile_strict_cost.json).  Not
+   covered: the drop-in fd_ed25519_verify, which is the reference's API and
+   keeps the reference's verdicts.
 
    fd_ed25519_amd_set_mode: FD_ED25519_AMD_OK, or FD_ED25519_AMD_ERR_INVAL
    for any other mode (nothing touches a device).  Call it between batches.

@@ -278,6 +278,34 @@ fd_verify_amd_tile_out_data_sz( fd_verify_amd_tile_t * tile );
 int
 fd_verify_amd_tile_set_framing( fd_verify_amd_tile_t * tile, int framing );
 
+/* Verdict mode (FD_ED25519_AMD_MODE_*, fd_ed25519_amd.h).  A new tile is in
+   FD_ED25519_AMD_MODE_REFERENCE: every frag gets the reference's verdict,
+   bit for bit.  FD_ED25519_AMD_MODE_STRICT gives every signature the strict
+   RFC 8032 verdict of the batch engine's strict mode (same rule, same
+   device function): s >= L -> FD_ED25519_ERR_SIG (the reference's s window
+   no longer verifies), a non-canonical or small-order A or R ->
+   FD_ED25519_ERR_PUBKEY, the group equation compared by value (the
+   reference's false rejects verify).  Set between runs, like the framing;
+   it takes effect at the next run's launch, which starts the strict
+   instantiation of the persistent kernel (k_tile_persist_strict: the same
+   loop, the overlay run inside every chunk before its results are stored)
+   instead of k_tile_persist.  A tile in reference mode launches what it
+   always did.  Everything downstream of the verdict follows the strict
+   verdict: what is published, sv_filt_cnt / sv_filt_sz,
+   sv_filt_code_cnt[3] and the verdict log.  TXN framing keeps its rule (the
+   first failing signature's code in signature order) over the strict
+   codes.  Unchanged: HA dedup, bad-frag handling, FD_TXN_AMD_ERR_PARSE,
+   the tags, ordering, flow control, the chunk levels and their thresholds.
+   Any other mode, or a NULL tile: FD_ED25519_AMD_ERR_INVAL (the mode stays
+   as it was).  fd_verify_amd_tile_verdict_mode returns the mode the next
+   run will use (ERR_INVAL for a NULL tile).  (fd_verify_amd_tile_mode below
+   is the chunk-mode rule, not this.) */
+int
+fd_verify_amd_tile_set_verdict_mode( fd_verify_amd_tile_t * tile, int mode );
+
+int
+fd_verify_amd_tile_verdict_mode( fd_verify_amd_tile_t const * tile );
+
 /* Input staging.
    Copy mode (default): the tile copies each input frag into its own output
    frame, re-checks the frag's mcache line afterwards (a frag lapped during
@@ -490,6 +518,8 @@ fd_verify_amd_tile_pack( uint const * slots, ulong cnt, int thr, ulong * nsl );
 #define FD_VERIFY_AMD_BENCH_CHUNK_QUAD   (1024) /* chunk_mode QUAD */
 #define FD_VERIFY_AMD_BENCH_STALL_HELPER (512) /* test hook: the copy helper spins 200 us before every 4th
                                                  block it claims, so the stager re-copies blocks (out[41]) */
+#define FD_VERIFY_AMD_BENCH_STRICT       (2048) /* the tile runs in FD_ED25519_AMD_MODE_STRICT; the caller passes
+                                                   the strict verdicts as expect_err */
 
 int
 fd_verify_amd_bench_stream( int           device,
