@@ -120,6 +120,8 @@ fd_ed25519_amd_new( int device, ulong batch_max, ulong blob_max ) {
   e->device = device; e->cap = batch_max; e->blob_cap = blob_max; e->nslot = nslot;
   ev = getenv( "FD_ED25519_AMD_GATHER_COPY" );
   e->gather_copy = ev && atoi( ev ) == 1;
+  ev = getenv( "FD_ED25519_AMD_GATHER_TXN_WAVES" );
+  e->gather_txn_waves = ( ev && atoi( ev ) >= 1 && atoi( ev ) <= 65536 ) ? atoi( ev ) : 64;
   /* the pinned staging on the GPU's NUMA node (the thread's own policy is
      restored afterwards; fd_numa.cpp) */
   int pmode = 0; unsigned long pmask[16];
@@ -262,6 +264,8 @@ slot_launch_packed( slot_t * s, ulong n, ulong blob_sz, schar * out, ulong * tag
    verdicts land in h_terr, per-signature ones (when s_out) in h_err; the
    per-transaction tags (when tt_out) in h_ttag, the per-signature ones (when
    st_out) in h_tag. */
+static int slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, schar * t_out, schar * s_out, ulong * tt_out, ulong * st_out );
+
 static int
 slot_launch_txn( slot_t * s, ulong c, ulong nslot, ulong blob_sz, schar * t_out, schar * s_out, ulong * tt_out,
                  ulong * st_out ) {
@@ -269,6 +273,14 @@ slot_launch_txn( slot_t * s, ulong c, ulong nslot, ulong blob_sz, schar * t_out,
   HIPCHK( hipMemcpyAsync( s->d_tsz,   s->h_tsz,   4UL*c,        hipMemcpyHostToDevice, s->stream ) );
   HIPCHK( hipMemcpyAsync( s->d_tbase, s->h_tbase, 4UL*(c+1UL),  hipMemcpyHostToDevice, s->stream ) );
   if( blob_sz ) HIPCHK( hipMemcpyAsync( s->d_blob, s->h_blob, blob_sz, hipMemcpyHostToDevice, s->stream ) );
+  return slot_launch_txn_dev( s, c, nslot, t_out, s_out, tt_out, st_out );
+}
+
+/* The kernels of a transaction chunk whose payloads and planes (d_blob,
+   d_toff, d_tsz, d_tbase[0..c]) are on the device, or on their way there on
+   the slot's stream: parse, verify with d_skip, reduce, outputs, tags. */
+static int
+slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, schar * t_out, schar * s_out, ulong * tt_out, ulong * st_out ) {
   if( fd_amd_launch_txn_parse( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, s->d_fp, NULL, 0, s->d_tbase,
                                s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_skip, s->stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
@@ -785,6 +797,141 @@ fd_ed25519_amd_verify_txns_tag( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const
     s->h_tbase[c] = (uint32_t)ns;
     rc = slot_launch_txn( s, c, ns, bsz, txn_err + t, sig_err ? sig_err + gsig : NULL, txn_tag ? txn_tag + t : NULL,
                           sig_tag ? sig_tag + gsig : NULL );
+    gsig += ns;
+    return rc ? rc : (long)c;
+  } );
+}
+
+/* ------------------------------------------------------------------ */
+/* transaction batches gathered by the GPU from registered memory       */
+
+extern "C" ulong
+fd_ed25519_amd_txn_slots_ptrs( ulong txn_cnt, void const * const * txn, ulong const * txn_sz, uint * tbase ) {
+  ulong acc = 0;
+  for( ulong t=0; t<txn_cnt; t++ ) {
+    tbase[t] = (uint)acc;
+    if( txn_sz[t] && txn[t] ) acc += fd_amd_txn_slots1( (uchar const *)txn[t], txn_sz[t] );
+  }
+  tbase[txn_cnt] = (uint)acc;
+  return acc;
+}
+
+/* The one place that sizes a gathered transaction chunk: fd_ed25519_amd_gather_layout's
+   rule with the signature slots as a third bound (every payload fits a chunk
+   alone: the callers check its size and its slots up front).  dst[j]:
+   payload j's offset in the chunk's blob, a multiple of 16; it owns
+   [dst[j], dst[j] + round_up( sz[j], 16 )).  Pure host code. */
+extern "C" ulong
+fd_ed25519_amd_txn_gather_layout( ulong n, ulong const * sz, uint const * slots, ulong cap, ulong blob_cap, uint * dst,
+                                  ulong * slot_cnt ) {
+  ulong c = 0, b = 0, ns = 0;
+  while( c < n ) {
+    ulong const pad = (sz[c] + 15UL) & ~15UL;
+    if( c && ( c >= cap || ns + slots[c] > cap || sz[c] > blob_cap || b + pad > blob_cap ) ) break;
+    dst[c] = (uint)b;
+    b += pad; ns += slots[c]; c++;
+  }
+  *slot_cnt = ns;
+  return c;
+}
+
+/* Chunk of c transactions whose records sit in s->h_pack: k_gather_txn
+   fetches the payloads into d_blob and writes d_toff, d_tsz and
+   d_tbase[0..c] (d_tbase[c] = nslot), then the kernels of slot_launch_txn --
+   without its four host-to-device copies: the records reach the kernel in
+   place (it reads the mapped h_pack, 32 B per transaction, once), as
+   slot_launch_gather's do. */
+static int
+slot_launch_txn_gather( slot_t * s, ulong c, ulong nslot, uint waves, schar * t_out, schar * s_out, ulong * tt_out,
+                        ulong * st_out ) {
+  /* A throughput chunk's gather runs beside the other slots' verify kernels
+     and its reads of host memory hold up their memory traffic
+     (slot_launch_gather): capped at `waves` waves, 64 unless
+     FD_ED25519_AMD_GATHER_TXN_WAVES says otherwise (32 / 64 / 128 measured:
+     profiles/txns_registered_cost.json).  A chunk small enough for the
+     latency kernels is a batch of its own with nothing beside it: no cap. */
+  bool const lat = fd_amd_uses_latency_path( (uint32_t)nslot, 0 ) != 0;
+  if( fd_amd_launch_gather_txn( (uint32_t)c, (fd_amd_gather_txn_rec_t const *)s->m_pack, s->d_blob, s->d_toff, s->d_tsz,
+                                s->d_tbase, (uint32_t)nslot, lat ? 0u : waves, s->stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  return slot_launch_txn_dev( s, c, nslot, t_out, s_out, tt_out, st_out );
+}
+
+extern "C" int
+fd_ed25519_amd_verify_txns_registered( fd_ed25519_amd_t * e, ulong txn_cnt, void const * const * txn, ulong const * txn_sz,
+                                       schar * txn_err, uint * sig_base, schar * sig_err ) {
+  return fd_ed25519_amd_verify_txns_registered_tag( e, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, NULL, NULL );
+}
+
+extern "C" int
+fd_ed25519_amd_verify_txns_registered_tag( fd_ed25519_amd_t * e, ulong txn_cnt, void const * const * txn,
+                                           ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                                           ulong * txn_tag, ulong * sig_tag ) {
+  if( !e || (txn_cnt && (!txn || !txn_sz || !txn_err)) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( (sig_err || sig_tag) && !sig_base ) return FD_ED25519_AMD_ERR_INVAL;
+  if( txn_cnt > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !txn_cnt ) { if( sig_base ) sig_base[0] = 0U; return FD_ED25519_AMD_OK; }
+  reg_view_t view;
+  /* every transaction before anything launches: its pointer, its size, its
+     first and last byte in one registration of the table, and the signature
+     slots it reserves -- read here, once, from payload[0]: the chunks and
+     sig_base use this count, whatever the byte holds later */
+  std::vector<uint> slots( txn_cnt );
+  auto check = [&]( ulong lo, ulong hi ) -> bool {
+    reg_view_t v = view;                     /* its own last-hit index */
+    for( ulong t=lo; t<hi; t++ ) {
+      ulong const sz = txn_sz[t];
+      uint64_t dev;
+      if( !sz ) { slots[t] = 0U; continue; }
+      if( sz > FD_TXN_AMD_MTU || sz > e->blob_cap || !txn[t] || !v.xlat( txn[t], sz, &dev ) ) return false;
+      ulong const k = fd_amd_txn_slots1( (uchar const *)txn[t], sz );
+      if( k > e->cap ) return false;
+      slots[t] = (uint)k;
+    }
+    return true;
+  };
+  /* the pass reads 16 B of pointer and size and one payload byte per
+     transaction and nothing of it overlaps the GPU: large batches split it
+     over up to 4 host threads, as fd_ed25519_amd_verify_batch_registered */
+  int nt = (int)( txn_cnt >> 17 ); if( nt > 4 ) nt = 4;
+  if( nt < 2 ) { if( !check( 0UL, txn_cnt ) ) return FD_ED25519_AMD_ERR_INVAL; }
+  else {
+    std::thread th[3]; bool ok[4];
+    ulong const part = ( txn_cnt + (ulong)nt - 1UL ) / (ulong)nt;
+    for( int t=1; t<nt; t++ ) th[t-1] = std::thread( [&, t]{ ok[t] = check( part*(ulong)t, std::min( txn_cnt, part*(ulong)(t+1) ) ); } );
+    ok[0] = check( 0UL, part );
+    for( int t=1; t<nt; t++ ) th[t-1].join();
+    for( int t=0; t<nt; t++ ) if( !ok[t] ) return FD_ED25519_AMD_ERR_INVAL;
+  }
+  /* global signature numbering (the caller-visible sig_base) */
+  if( sig_base ) {
+    ulong acc = 0;
+    for( ulong t=0; t<txn_cnt; t++ ) { sig_base[t] = (uint)acc; acc += slots[t]; }
+    sig_base[txn_cnt] = (uint)acc;
+  }
+  ulong gsig = 0;
+  return run_ring( e, e->nslot, txn_cnt, [&]( slot_t * s, ulong t ) -> long {
+    int rc = slot_alloc_aux( s, e->cap );
+    if( !rc && (txn_tag || sig_tag) ) rc = slot_alloc_tag( s, e->cap );
+    if( rc ) return rc;
+    /* the chunk's records in h_pack (32 B per transaction), their dst behind them */
+    fd_amd_gather_txn_rec_t * rec = (fd_amd_gather_txn_rec_t *)s->h_pack;
+    uint * dst = (uint *)(s->h_pack + 32UL*e->cap);
+    ulong ns = 0;
+    ulong c = fd_ed25519_amd_txn_gather_layout( txn_cnt - t, txn_sz + t, slots.data() + t, e->cap, e->blob_cap, dst, &ns );
+    ulong b = 0;
+    for( ulong j=0; j<c; j++ ) {
+      /* translated again, not kept from the check (fd_ed25519_amd_verify_batch_registered):
+         an address the table does not give never reaches the kernel */
+      ulong const sz = txn_sz[t+j];
+      rec[j].src = 0UL;
+      if( sz > FD_TXN_AMD_MTU || sz > e->blob_cap || ( sz && ( !txn[t+j] || !view.xlat( txn[t+j], sz, &rec[j].src ) ) ) )
+        return FD_ED25519_AMD_ERR_INVAL;
+      rec[j].sz = (uint32_t)sz; rec[j].dst = dst[j]; rec[j].tbase = (uint32_t)b;
+      b += slots[t+j];
+    }
+    rc = slot_launch_txn_gather( s, c, ns, (uint)e->gather_txn_waves, txn_err + t, sig_err ? sig_err + gsig : NULL,
+                                 txn_tag ? txn_tag + t : NULL, sig_tag ? sig_tag + gsig : NULL );
     gsig += ns;
     return rc ? rc : (long)c;
   } );

@@ -58,6 +58,8 @@ struct fd_ed25519_amd {
   int    mode;       /* FD_ED25519_AMD_MODE_*: mirrored into every slot's `strict` */
   int    gather_copy;/* verify_batch_registered: 0 k_gather reads a chunk's records in the mapped h_pack (default),
                         1 they go to d_pack by one H2D first (FD_ED25519_AMD_GATHER_COPY=1: the A/B of tools/batch_registered_cost.py) */
+  int    gather_txn_waves; /* verify_txns_registered: wave cap of a throughput chunk's k_gather_txn, 64 (default), or
+                              FD_ED25519_AMD_GATHER_TXN_WAVES in [1, 65536] (the A/B of tools/txns_registered_cost.py) */
   slot_t slot[FD_AMD_SLOT_MAX];
 };
 

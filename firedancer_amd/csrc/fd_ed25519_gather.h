@@ -1,6 +1,8 @@
 /* firedancer_amd/csrc/fd_ed25519_gather.h -- k_gather: fetch the records of
    a pointer-array chunk from registered host memory into the slot's device
-   planes (fd_ed25519_amd_verify_batch_registered).
+   planes (fd_ed25519_amd_verify_batch_registered); k_gather_txn, below it,
+   does the same for the payloads of a transaction chunk
+   (fd_ed25519_amd_verify_txns_registered).
 
    Input: one fd_amd_gather_rec_t per signature, { pub, sig, msg, sz, dst }:
    the device addresses of its 32 public-key, 64 signature and sz message
@@ -174,6 +176,117 @@ k_gather( u32 n, fd_amd_gather_rec_t const * __restrict__ rec, u8 * __restrict__
   st_msg( 0u );
   /* messages past 16 GATHER_R words; wave-uniform trip count (the shuffles need every lane), bounded by sz <= blob_max */
   for( u32 t0 = 16u*GATHER_R; __any( t0 < nOmax ); t0 += 16u*GATHER_R ) { ld_msg( t0 ); st_msg( t0 ); }
+
+  }
+}
+
+/* k_gather_txn: fetch the payloads of a pointer-array transaction chunk from
+   registered host memory into the slot's device blob and write the chunk's
+   transaction planes (fd_ed25519_amd_verify_txns_registered).
+
+   Input: one fd_amd_gather_txn_rec_t per transaction, { src, sz, dst, tbase }:
+   the device address of its sz payload bytes (translated on the host from
+   the registration table, the only source of addresses this kernel is ever
+   given), the offset the payload gets in d_blob and its first signature
+   slot.  Output: the payload at d_blob + dst, d_toff[t] = dst, d_tsz[t] = sz,
+   d_tbase[t] = tbase and d_tbase[n] = slot_cnt (a kernel argument) -- what
+   k_txn_parse, k_txn_reduce and k_tag_gather read, so the chunk needs no
+   host-to-device copy.
+
+   ACCESS INVARIANT.  Every load from caller memory is a naturally aligned
+   16-B word that contains at least one byte of the range being copied:
+     - word t starts at (s & ~15) + 16 t <= s + 16 t, and it is loaded only
+       for t < nA, i.e. 16 t < (s & 15) + len, i.e. its first byte lies
+       before s + len; for t = 0 it ends after s, for t > 0 it starts after
+       s: so it overlaps [s, s + len);
+     - len = 0 loads nothing (nA is forced to 0, whatever s & 15 is);
+     - a lane that needs the word after its own (sh != 0) takes it from the
+       lane that loaded it (one shuffle), so no word is loaded twice and no
+       lane loads a word "just in case";
+     - a lane with no such word to fetch in some load instruction (t >= nA)
+       loads the first 16 B of d_blob instead -- the slot's own device
+       memory, the value never used for a byte that counts (gather_ld).  That keeps the kernel free
+       of branches: around a predicated load the compiler branches, and
+       after such a branch it waits with vmcnt(0) for loads still on their
+       way.
+   An aligned 16-B word never straddles a page, so a payload flush against
+   the first or last byte of a registration is read without touching the
+   neighbouring pages.  Bytes of such a word outside the range (at most 15
+   before and 15 after) are read and, behind a payload's last byte, land in
+   that payload's own padding in d_blob; the parser reads [dst, dst + sz)
+   alone.
+
+   Destinations: dst is a multiple of 16 and a payload owns
+   [dst, dst + round_up( sz, 16 )) of d_blob
+   (fd_ed25519_amd_txn_gather_layout), so whole 16-B stores never touch a
+   neighbour; d_blob keeps its 64-B tail slack.
+
+   Shape: k_gather's.  16 lanes per record, lane j takes aligned words j,
+   j + 16, ...; each 16-lane group has GATHER_G records in flight and every
+   load of them is issued before the first store; a wave takes blocks of
+   4 GATHER_G records gridDim.x apart, so the grid bounds the host-memory
+   reads in flight.  ONE pass: a payload is at most FD_TXN_AMD_MTU bytes,
+   which span at most 78 aligned words, and the pass loads 16 GATHER_R = 80.
+   The entry point is the only producer of records and has refused larger
+   sizes, so there is no further-pass loop (a larger sz would be copied
+   short, never out of bounds: stores stay below word 16 GATHER_R of the
+   payload's own, then larger, range).  Output word u < nO takes aligned
+   words u and u + 1; u + 1 is a word of the range only when u + 1 < nA <=
+   16 GATHER_R, so no lane needs a word past the pass (k_gather's extra word
+   GATHER_R is not loaded).  No atomics, no spinning, vector stores only. */
+static_assert( ((15UL + FD_TXN_AMD_MTU + 15UL) >> 4) <= 16UL*GATHER_R,
+               "k_gather_txn copies a payload in one pass of 16 GATHER_R aligned words" );
+
+__global__ void __launch_bounds__(64)
+k_gather_txn( u32 n, fd_amd_gather_txn_rec_t const * __restrict__ rec, u8 * __restrict__ d_blob, u32 * __restrict__ d_toff,
+              u32 * __restrict__ d_tsz, u32 * __restrict__ d_tbase, u32 slot_cnt ) {
+  u32 const l = threadIdx.x, g = l >> 4, j = l & 15u;
+  u32 const nblk = (n + 4u*GATHER_G - 1u) / (4u*GATHER_G);
+  if( !blockIdx.x && !l ) d_tbase[n] = slot_cnt;
+  /* a wave takes blocks of 4 GATHER_G records, gridDim.x apart: the grid, not n, bounds the reads in flight */
+  for( u32 blk = blockIdx.x; blk < nblk; blk += gridDim.x ) {
+
+  /* the group's records: record h of group g is transaction 4 GATHER_G block + 4 h + g */
+  u32 idx[GATHER_G], sz[GATHER_G], dst[GATHER_G], tb[GATHER_G], nA[GATHER_G], nO[GATHER_G];
+  u64 src[GATHER_G];
+  _Pragma("unroll") for( int h=0; h<GATHER_G; h++ ) {
+    idx[h] = blk * (4u*GATHER_G) + 4u*(u32)h + g;
+    bool const live = idx[h] < n;
+    uint4 const * rp = (uint4 const *)(rec + (live ? idx[h] : 0u));
+    uint4 const r0 = rp[0], r1 = rp[1];
+    src[h] = ((u64)r0.y << 32) | r0.x;
+    sz[h] = live ? r0.z : 0u;  dst[h] = r0.w;  tb[h] = r1.x;
+    if( !live ) idx[h] = 0xFFFFFFFFu;
+    nO[h] = (sz[h] + 15u) >> 4;                                         /* sz <= FD_TXN_AMD_MTU */
+    nA[h] = sz[h] ? (u32)(((u32)src[h] & 15u) + sz[h] + 15u) >> 4 : 0u;  /* no bytes: no word */
+  }
+
+  /* aligned words [0, 16 GATHER_R) of every record: the loads, then the stores */
+  uint4 v[GATHER_G][GATHER_R];
+  _Pragma("unroll") for( int h=0; h<GATHER_G; h++ ) {
+    _Pragma("unroll") for( int r=0; r<GATHER_R; r++ ) {
+      u32 const t = 16u*(u32)r + j;
+      v[h][r] = gather_ld( src[h], t, t < nA[h], d_blob );
+    }
+  }
+  _Pragma("unroll") for( int h=0; h<GATHER_G; h++ ) {
+    uint4 * const o = (uint4 *)(d_blob + dst[h]);
+    u32 const sh = (u32)src[h] & 15u;
+    _Pragma("unroll") for( int r=0; r<GATHER_R; r++ ) {
+      /* the next aligned word: lane j + 1's of this batch, for lane 15 lane 0's of the next batch
+         (the last batch has none: its lane 15 is word 16 GATHER_R - 1 >= nO, never stored) */
+      uint4 give = v[h][r];
+      if( r + 1 < GATHER_R ) {   /* compile time; bit selects, not ?: (gather_shift) */
+        uint4 const nx = v[h][r + 1 < GATHER_R ? r + 1 : r];
+        u32 const m = 0u - (u32)!j;
+        give = make_uint4( (nx.x & m) | (give.x & ~m), (nx.y & m) | (give.y & ~m), (nx.z & m) | (give.z & ~m), (nx.w & m) | (give.w & ~m) );
+      }
+      uint4 const hi = gather_shfl( give, j == 15u ? l - 15u : l + 1u );
+      u32 const t = 16u*(u32)r + j;
+      if( t < nO[h] ) o[t] = gather_shift( v[h][r], hi, sh );
+    }
+    if( !j && idx[h] != 0xFFFFFFFFu ) { d_toff[idx[h]] = dst[h]; d_tsz[idx[h]] = sz[h]; d_tbase[idx[h]] = tb[h]; }
+  }
 
   }
 }

@@ -178,6 +178,19 @@ typedef struct { uint64_t pub, sig, msg; uint32_t sz, dst; } fd_amd_gather_rec_t
 int fd_amd_launch_gather( uint32_t n, fd_amd_gather_rec_t const * d_rec, uint8_t * d_pub, uint8_t * d_sig,
                           uint32_t * d_off, uint32_t * d_sz, uint8_t * d_blob, uint32_t waves, hipStream_t stream );
 
+/* k_gather_txn (fd_ed25519_gather.h): n records -> the transaction planes.
+   A record is one payload of a pointer-array transaction chunk: src, the
+   DEVICE address of its sz <= FD_TXN_AMD_MTU bytes (unused when sz is 0),
+   any byte alignment, in host memory the GPU can read; dst: a multiple of
+   16, the payload's offset in d_blob, which owns
+   [dst, dst + round_up( sz, 16 )) there; tbase: its first signature slot.
+   d_rec: 32-aligned device or mapped host memory.  Writes d_blob[dst ..],
+   d_toff[t] = dst, d_tsz[t] = sz, d_tbase[t] = tbase and
+   d_tbase[n] = slot_cnt.  At most `waves` waves (0: no cap). */
+typedef struct { uint64_t src; uint32_t sz, dst, tbase, pad[3]; } fd_amd_gather_txn_rec_t;
+int fd_amd_launch_gather_txn( uint32_t n, fd_amd_gather_txn_rec_t const * d_rec, uint8_t * d_blob, uint32_t * d_toff,
+                              uint32_t * d_tsz, uint32_t * d_tbase, uint32_t slot_cnt, uint32_t waves, hipStream_t stream );
+
 /* n bytes device -> mapped host memory by a kernel (no DMA engine). */
 int fd_amd_launch_copy_out( void * d_dst_mapped, void const * d_src, size_t n, hipStream_t stream );
 

@@ -28,7 +28,7 @@
  *   fd_ed25519_pool.h   k_ai, k_dsmp, k_fin (large batches)
  *   fd_ed25519_tile.h   k_tile_persist, k_tile_synth
  *   fd_ed25519_strict.h k_strict (strict mode's overlay, after the DSM stage)
- *   fd_ed25519_gather.h k_gather (pointer-array chunks from registered memory)
+ *   fd_ed25519_gather.h k_gather, k_gather_txn (pointer-array chunks from registered memory)
  * This file keeps the launch code, the batch-size policy and the small
  * kernels that move results out (k_copy_out: verdicts; k_tag_out /
  * k_tag_gather: the dedup tags k_prep left in the workspace).
@@ -47,6 +47,7 @@
 #include "fd_ed25519_pool.h"
 #include "fd_ed25519_tile.h"
 #include "fd_ed25519_strict.h"
+#include "../../include/fd_txn_amd.h"   /* FD_TXN_AMD_MTU: k_gather_txn's one pass */
 #include "fd_ed25519_gather.h"
 
 /* ------------------------------------------------------------------ */
@@ -98,6 +99,18 @@ fd_amd_launch_gather( uint32_t n, fd_amd_gather_rec_t const * d_rec, uint8_t * d
   u32 nb = (n + per - 1u)/per;
   if( waves && nb > waves ) nb = waves;
   hipLaunchKernelGGL( k_gather, dim3(nb), dim3(64), 0, stream, n, d_rec, d_pub, d_sig, d_off, d_sz, d_blob );
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* 4 GATHER_G payloads per wave, at most `waves` waves (0: no cap) (k_gather_txn, fd_ed25519_gather.h). */
+int
+fd_amd_launch_gather_txn( uint32_t n, fd_amd_gather_txn_rec_t const * d_rec, uint8_t * d_blob, uint32_t * d_toff,
+                          uint32_t * d_tsz, uint32_t * d_tbase, uint32_t slot_cnt, uint32_t waves, hipStream_t stream ) {
+  if( !n ) return 0;
+  u32 const per = 4u*GATHER_G;
+  u32 nb = (n + per - 1u)/per;
+  if( waves && nb > waves ) nb = waves;
+  hipLaunchKernelGGL( k_gather_txn, dim3(nb), dim3(64), 0, stream, n, d_rec, d_blob, d_toff, d_tsz, d_tbase, slot_cnt );
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -164,6 +164,11 @@ def lib():
            "fd_ed25519_amd_verify_batch_registered": ([vp, ul, vp, vp, vp, vp, vp], i),
            "fd_ed25519_amd_verify_batch_registered_tag": ([vp, ul, vp, vp, vp, vp, vp, vp], i),
            "fd_ed25519_amd_gather_layout": ([ul, vp, ul, ul, vp], ul),
+           # transaction batches gathered by the GPU from registered memory
+           "fd_ed25519_amd_verify_txns_registered": ([vp, ul, vp, vp, vp, vp, vp], i),
+           "fd_ed25519_amd_verify_txns_registered_tag": ([vp, ul, vp, vp, vp, vp, vp, vp, vp], i),
+           "fd_ed25519_amd_txn_slots_ptrs": ([ul, vp, vp, vp], ul),
+           "fd_ed25519_amd_txn_gather_layout": ([ul, vp, vp, ul, ul, vp, vp], ul),
            # the streaming tile's verdict mode
            "fd_verify_amd_tile_set_verdict_mode": ([vp, i], i), "fd_verify_amd_tile_verdict_mode": ([vp], i),
            # debug: k_dsmp's grid, the parked R'
@@ -426,6 +431,93 @@ class Engine:
         first signature's dedup tag, 0 where it did not parse) and per
         signature slot (the numbering of sig_err / txn_slots)."""
         return _verify_txns("fd_ed25519_amd_verify_txns", self._h, payload, txn_off, txn_sz, want_sigs, want_tags)
+
+    def verify_txns_ptrs(self, txn_ptr, txn_sz, want_sigs=False, want_tags=False):
+        """fd_ed25519_amd_verify_txns_registered: the transaction batch in
+        pointer-array form with no host staging.  txn_ptr: uint64 array of
+        host addresses (txn_sz[t] payload bytes behind each, any alignment),
+        every non-empty range inside one host_register registration; the GPU
+        fetches the payloads itself.  Returns what verify_txns returns for
+        the same payloads."""
+        tp = np.ascontiguousarray(txn_ptr, np.uint64)
+        sz = np.ascontiguousarray(txn_sz, np.uint64)
+        n = int(tp.size)
+        assert sz.size == n
+        if ((tp == 0) & (sz != 0)).any():     # refused by the library too; the slot count below would read the bytes
+            raise EngineError("verify_txns_ptrs: NULL payload pointer with a size")
+        terr = np.zeros(max(n, 1), np.int8)
+        base = serr = None
+        if want_sigs or want_tags:
+            base, tot = txn_slots_ptrs(tp, sz)
+        if want_sigs:
+            serr = np.zeros(max(tot, 1), np.int8)
+        args = (self._h, n, _ptr(tp), _ptr(sz), _ptr(terr), _ptr(base) if base is not None else None,
+                _ptr(serr) if want_sigs else None)
+        if want_tags:
+            ttag, stag = np.zeros(max(n, 1), np.uint64), np.zeros(max(tot, 1), np.uint64)
+            rc = lib().fd_ed25519_amd_verify_txns_registered_tag(*args, _ptr(ttag), _ptr(stag))
+        else:
+            rc = lib().fd_ed25519_amd_verify_txns_registered(*args)
+        if rc:
+            raise EngineError("fd_ed25519_amd_verify_txns_registered rc=%d" % rc)
+        out = (terr[:n],)
+        if want_sigs:
+            out += (base, serr[:int(base[-1])])
+        if want_tags:
+            out += (ttag[:n], stag[:int(base[-1])])
+        return out if len(out) > 1 else out[0]
+
+    def verify_txns_registered(self, arena, txn_off, txn_sz, want_sigs=False, want_tags=False):
+        """verify_txns_ptrs over one registered uint8 arena (host_register):
+        transaction t is arena[txn_off[t] : + txn_sz[t]]."""
+        assert arena.dtype == np.uint8 and arena.flags["C_CONTIGUOUS"]
+        base = np.uint64(arena.ctypes.data)
+        return self.verify_txns_ptrs(base + np.asarray(txn_off, np.uint64), txn_sz, want_sigs=want_sigs,
+                                     want_tags=want_tags)
+
+
+def txn_slots_ptrs(txn_ptr, txn_sz):
+    """fd_ed25519_amd_txn_slots_ptrs: (tbase[txn_cnt+1], total signature slots)
+    of a pointer-array batch; reads the first byte behind every pointer with
+    a size (no device)."""
+    tp = np.ascontiguousarray(txn_ptr, np.uint64)
+    sz = np.ascontiguousarray(txn_sz, np.uint64)
+    assert tp.size == sz.size
+    base = np.zeros(tp.size + 1, np.uint32)
+    tot = lib().fd_ed25519_amd_txn_slots_ptrs(int(tp.size), _ptr(tp), _ptr(sz), _ptr(base))
+    return base, int(tot)
+
+
+def txn_gather_layout(sz, slots, cap, blob_cap):
+    """Python mirror of fd_ed25519_amd_txn_gather_layout: how
+    verify_txns_registered sizes one chunk.  Of the payload sizes sz with
+    signature-slot counts slots the chunk takes the first, always, and
+    further ones while the count stays <= cap, the slot total stays <= cap
+    and the padded byte total, the sum of the sizes rounded up to 16, stays
+    <= blob_cap.  Returns (count, dst, slot_cnt): dst uint32 (count,), each
+    payload's offset in the chunk's blob."""
+    dst, b, ns = [], 0, 0
+    for s, k in zip(sz, slots):
+        s, k = int(s), int(k)
+        pad = (s + 15) & ~15
+        if dst and (len(dst) >= cap or ns + k > cap or s > blob_cap or b + pad > blob_cap):
+            break
+        dst.append(b)
+        b += pad
+        ns += k
+    return len(dst), np.asarray(dst, np.uint32), ns
+
+
+def txn_gather_layout_c(sz, slots, cap, blob_cap):
+    """fd_ed25519_amd_txn_gather_layout itself (the library's; no device)."""
+    sz = np.ascontiguousarray(sz, np.uint64)
+    slots = np.ascontiguousarray(slots, np.uint32)
+    assert sz.size == slots.size
+    dst = np.zeros(max(sz.size, 1), np.uint32)
+    ns = ctypes.c_ulong(0)
+    c = int(lib().fd_ed25519_amd_txn_gather_layout(int(sz.size), _ptr(sz), _ptr(slots), int(cap), int(blob_cap),
+                                                   _ptr(dst), ctypes.byref(ns)))
+    return c, dst[:c], int(ns.value)
 
 
 def txn_slots(payload, txn_off, txn_sz):

@@ -227,6 +227,94 @@ fd_ed25519_amd_multi_verify_txns_tag( fd_ed25519_amd_multi_t * multi,
                                       ulong *                  txn_tag,
                                       ulong *                  sig_tag );
 
+/* Transaction batch from registered memory: fd_ed25519_amd_verify_txns
+   [_tag] in pointer-array form and without its staging.  txn[t] and a ulong
+   txn_sz[t] replace payload, txn_off, txn_sz and payload_sz; every output
+   is exactly that of fd_ed25519_amd_verify_txns[_tag] for the same payloads:
+   the same txn_err codes (FD_TXN_AMD_ERR_PARSE included), the same global
+   sig_base numbering (fd_ed25519_amd_txn_slots_ptrs), the same sig_err,
+   txn_tag and sig_tag, with the engine's verdict mode applied.  The
+   untagged function is the tagged one with both tag pointers NULL.
+
+   The host copies no payload byte.  Per chunk it writes one 32-B record per
+   transaction (a device address, the size, an offset, the signature-slot
+   base) and a kernel (k_gather_txn) fetches the payloads over PCIe into the
+   device blob that the GPU parser and the verify kernels read, and writes
+   the chunk's offset, size and slot planes itself: a chunk needs no
+   host-to-device copy.  Chunks are cut by fd_ed25519_amd_txn_gather_layout
+   and go through every engine slot (FD_ED25519_AMD_NSLOT).
+
+   Requirement: every non-empty [txn[t], +txn_sz[t]) lies inside ONE
+   registration made through fd_ed25519_amd_host_register (its first and its
+   last byte in the same one; two adjacent registrations do not make one
+   range; only that table is consulted, as for
+   fd_ed25519_amd_verify_batch_registered).  Payloads may have any byte
+   alignment, may repeat and may overlap.  txn[t] is not looked at when
+   txn_sz[t] is 0; such a payload gets FD_TXN_AMD_ERR_PARSE.
+
+   Every transaction is checked before anything launches: a NULL array, a
+   NULL txn[t] with txn_sz[t] > 0, txn_sz[t] > FD_TXN_AMD_MTU or > blob_max,
+   a payload that reserves more than batch_max signature slots, sig_err or
+   sig_tag given without sig_base, or a range the table does not hold
+   returns FD_ED25519_AMD_ERR_INVAL with every output untouched and nothing
+   in flight.  Addresses are translated again per chunk; the GPU is never
+   given an address the table did not produce.
+
+   Memory that changes during the call is the caller's error, but the result
+   fails closed: the host reserves payload[0] signature slots from a byte it
+   read before the GPU fetched the payload, and the GPU parser rejects
+   (FD_TXN_AMD_ERR_PARSE) a transaction whose parsed signature count differs
+   from its reserved slots and writes only inside them, so no signature is
+   verified in, and no verdict is written to, a slot the host did not
+   reserve for that transaction. */
+int
+fd_ed25519_amd_verify_txns_registered( fd_ed25519_amd_t *   eng,
+                                       ulong                txn_cnt,
+                                       void const * const * txn,
+                                       ulong const *        txn_sz,
+                                       schar *              txn_err,
+                                       uint *               sig_base,
+                                       schar *              sig_err );
+
+int
+fd_ed25519_amd_verify_txns_registered_tag( fd_ed25519_amd_t *   eng,
+                                           ulong                txn_cnt,
+                                           void const * const * txn,
+                                           ulong const *        txn_sz,
+                                           schar *              txn_err,
+                                           uint *               sig_base,
+                                           schar *              sig_err,
+                                           ulong *              txn_tag,
+                                           ulong *              sig_tag );
+
+/* Signature-slot numbering of a pointer-array batch (pure host code, no
+   device): the rule of fd_ed25519_amd_txn_slots, one payload per pointer.
+   txn[t] is not looked at when txn_sz[t] is 0, and a NULL txn[t] reserves
+   no slot.  tbase has txn_cnt+1 entries; returns the total. */
+ulong
+fd_ed25519_amd_txn_slots_ptrs( ulong                txn_cnt,
+                               void const * const * txn,
+                               ulong const *        txn_sz,
+                               uint *               tbase );
+
+/* How fd_ed25519_amd_verify_txns_registered cuts a batch into chunks (pure
+   host code, no device): of n payloads with sizes sz[] and signature-slot
+   counts slots[], one chunk takes the first -- always -- and further ones
+   while the count stays <= cap, the slot total stays <= cap (the engine's
+   batch_max bounds both) and the padded byte total, the sum of
+   round_up( sz[i], 16 ), stays <= blob_cap (its blob_max).  Returns the
+   number taken and writes dst[0 .. that), each payload's offset in the
+   chunk's device blob (a multiple of 16, ascending), and *slot_cnt, the
+   chunk's signature slots. */
+ulong
+fd_ed25519_amd_txn_gather_layout( ulong         n,
+                                  ulong const * sz,
+                                  uint const *  slots,
+                                  ulong         cap,
+                                  ulong         blob_cap,
+                                  uint *        dst,
+                                  ulong *       slot_cnt );
+
 /* Device-resident form (inputs already in HBM, caller's stream, no sync).
    Signature slots follow the same rule as fd_ed25519_amd_verify_txns:
    d_tbase[t] (txn_cnt+1 entries, slot_cnt = d_tbase[txn_cnt]) is what
