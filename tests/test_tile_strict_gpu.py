@@ -4,7 +4,8 @@ mode's parked-R' layout, both pair subs, the chunk edges, TXN framing's
 first-failing-signature rule and the stream bench, against the independent
 Python verifier tests/_strict_ref.py.  The mode is the tile's and a run's:
 a tile back in reference mode, and a second tile beside a strict one, give
-the reference's codes bit for bit."""
+the reference's codes bit for bit.  The directed edge corpus (tests/_edges.py)
+goes through every chunk mode in both verdict modes."""
 import hashlib
 import os
 import struct
@@ -377,3 +378,106 @@ def test_bench_stream_strict(golden, strict_golden):
     # the same stream in reference mode publishes another set: the flag is what made the difference
     ref = _oracle.verify_batch(b)
     assert int((ref != err).sum()) >= 760
+
+
+# ---- the directed edge corpus (tests/_edges.py; its verdict table is pinned in test_edges_cpu.py) ----
+
+FRAG_KEY = {LAT: "gpu_frag_lat_cnt", THR: "gpu_frag_thr_cnt", QUAD: "gpu_frag_quad_cnt"}
+IDS = {LAT: "lat", THR: "thr", QUAD: "quad"}
+
+
+@pytest.fixture(scope="module")
+def corpus():
+    """(names, batch, messages, {mode: verdicts}, tags) of the edge corpus:
+    the CPU oracle's verdicts for reference mode, the independent Python
+    verifier's for strict mode, hashlib's tags; computed once."""
+    import _edges
+    from firedancer_amd import ed25519
+    from test_tags_gpu import _hashlib_tags
+    names, b = _edges.corpus()
+    ref = _oracle.verify_batch(b)
+    strict = np.array(_strict_ref.verify_batch(b), np.int8)
+    assert len(b) == 274 and int((ref != strict).sum()) == 117
+    tags = _hashlib_tags(b)
+    for a in (ref, strict, tags):
+        a.setflags(write=False)
+    return names, b, [b.msg(i) for i in range(len(b))], {ed25519.MODE_REFERENCE: ref, ed25519.MODE_STRICT: strict}, tags
+
+
+@pytest.fixture(scope="module")
+def corpus_feed(corpus):
+    """The corpus as frags, in order, published once."""
+    names, b, msgs, _, _ = corpus
+    mc_in, dc, _, _, _ = _feed(b.pub, b.sig, msgs, np.arange(len(b)), 512)
+    return mc_in, dc
+
+
+def _check_corpus_run(names, idx, want, tags, log, diag, mc_out, chunk_mode):
+    n = len(idx)
+    bad = np.nonzero(log[:n] != want)[0]
+    assert bad.size == 0, (int(bad.size), [(names[idx[i]], int(want[i]), int(log[i])) for i in bad[:10]])
+    assert (log[n:] == 99).all()
+    acc = np.nonzero(want == 0)[0]
+    assert diag["in_cnt"] == n and diag["bad_frag_cnt"] == 0
+    assert diag["out_cnt"] == acc.size and diag["sv_filt_cnt"] == n - acc.size and _sv(diag) == _codes(want)[1:]
+    assert [int(mc_out[o]["seq"]) for o in range(acc.size)] == list(range(acc.size))
+    assert [int(mc_out[o]["sig"]) for o in range(acc.size)] == [int(tags[idx[i]]) for i in acc]
+    assert diag[FRAG_KEY[chunk_mode]] == n
+
+
+@pytest.mark.parametrize("chunk_mode", [LAT, THR, QUAD], ids=[IDS[m] for m in (LAT, THR, QUAD)])
+@pytest.mark.parametrize("strict", [False, True], ids=["reference", "strict"])
+@pytest.mark.parametrize("zero_copy", [False, True], ids=["copy", "zero_copy"])
+def test_tile_edge_corpus_per_chunk_mode(monkeypatch, corpus, corpus_feed, chunk_mode, strict, zero_copy):
+    """All 274 edge vectors (non-canonical and mixed-order points, a
+    half-right R', a neutral accumulator, near misses of the byte compares,
+    s around L) through a tile with every chunk forced to one mode, in
+    reference and in strict mode: the verdict log equals the mode's verdict
+    of every frag; out_cnt, the three per-code SV_FILT counts and the
+    published tags, in order, follow."""
+    from firedancer_amd import ed25519, tango
+    monkeypatch.setenv("FD_AMD_TILE_PAIRS", "1")
+    names, b, msgs, verdicts, tags = corpus
+    mode = ed25519.MODE_STRICT if strict else ed25519.MODE_REFERENCE
+    n = len(b)
+    mc_in, dc = corpus_feed
+    mc_out = tango.mcache_new(512)
+    tile = tango.VerifyTile(0, batch_max=512, tcache_depth=0, chunk_mode=chunk_mode, mode=mode)
+    if zero_copy:
+        tile.register_dcache(dc)
+    log = np.full(n + 64, 99, np.int8)
+    tile.set_verdict_log(log)
+    try:
+        assert tile.verdict_mode == mode
+        diag, _ = tile.run(mc_in, dc, 0, mc_out, 0, n)
+    finally:
+        tile.close()
+    _check_corpus_run(names, np.arange(n), verdicts[mode], tags, log, diag, mc_out, chunk_mode)
+    if chunk_mode == QUAD:
+        assert diag["quad_pair_cnt"] > 0
+
+
+@pytest.mark.parametrize("chunk_mode", [LAT, THR, QUAD], ids=[IDS[m] for m in (LAT, THR, QUAD)])
+@pytest.mark.parametrize("strict", [False, True], ids=["reference", "strict"])
+def test_tile_edge_corpus_chunk_edge(monkeypatch, corpus, chunk_mode, strict):
+    """n one past two whole chunks; the last frag, alone in its chunk, is a
+    non-canonical public key that decodes (reference -3, strict -2)."""
+    from firedancer_amd import ed25519, tango
+    monkeypatch.setenv("FD_AMD_TILE_PAIRS", "1")
+    names, b, msgs, verdicts, tags = corpus
+    mode = ed25519.MODE_STRICT if strict else ed25519.MODE_REFERENCE
+    n = 2 * SLOTS[chunk_mode] + 1
+    last = names.index("nc_a/p+18/1")
+    assert (verdicts[ed25519.MODE_REFERENCE][last], verdicts[ed25519.MODE_STRICT][last]) == (-3, -2)
+    idx = np.array([(11 * i) % len(b) for i in range(n - 1)] + [last], np.int64)       # a stride over every class
+    assert len(set(idx.tolist())) == n
+    mc_in, dc, _, _, _ = _feed(b.pub, b.sig, msgs, idx, 256)
+    mc_out = tango.mcache_new(256)
+    tile = tango.VerifyTile(0, batch_max=256, tcache_depth=0, chunk_mode=chunk_mode, mode=mode)
+    log = np.full(n + 64, 99, np.int8)
+    tile.set_verdict_log(log)
+    try:
+        diag, _ = tile.run(mc_in, dc, 0, mc_out, 0, n)
+    finally:
+        tile.close()
+    _check_corpus_run(names, idx, verdicts[mode][idx], tags, log, diag, mc_out, chunk_mode)
