@@ -1034,6 +1034,17 @@ fd_ed25519_amd_workspace_footprint( ulong n ) {
   return fd_amd_ws_layout( n ).total;
 }
 
+/* Host only: the layout the kernels are launched with, for tests that
+   look at (or fill) single planes of a workspace. */
+extern "C" void
+fd_ed25519_amd_debug_ws_layout( ulong n, ulong * out ) {
+  if( !out ) return;
+  ws_layout_t L = fd_amd_ws_layout( n );
+  size_t const v[ FD_ED25519_AMD_WS_LAYOUT_CNT ] = { L.N, L.dig, L.evn, L.top, L.A, L.R, L.Ai, L.st, L.tag, L.ds, L.init,
+                                                     L.ctr, L.total };
+  for( int k=0; k<FD_ED25519_AMD_WS_LAYOUT_CNT; k++ ) out[k] = (ulong)v[k];
+}
+
 extern "C" int
 fd_ed25519_amd_verify_dev_ev_mode( ulong n, uchar const * d_pub, uchar const * d_sig, uint const * d_msg_off,
                                    uint const * d_msg_sz, uchar const * d_blob, schar * d_err, void * d_ws,

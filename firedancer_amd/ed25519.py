@@ -173,7 +173,9 @@ def lib():
            "fd_verify_amd_tile_set_verdict_mode": ([vp, i], i), "fd_verify_amd_tile_verdict_mode": ([vp], i),
            # debug: k_dsmp's grid, the parked R'
            "fd_ed25519_amd_debug_set_pool_waves": ([ul], None),
-           "fd_ed25519_amd_debug_rprime_dev": ([ul, vp, i, vp, vp], i)}
+           "fd_ed25519_amd_debug_rprime_dev": ([ul, vp, i, vp, vp], i),
+           # debug: the workspace's plane offsets (host only)
+           "fd_ed25519_amd_debug_ws_layout": ([ul, c_ulong_p], None)}
     for name, (args, res) in opt.items():
         if hasattr(L, name) or not os.environ.get("FD_AMD_LIB"):
             f = getattr(L, name)
@@ -698,6 +700,18 @@ def host_unregister(arr):
 
 def workspace_footprint(n):
     return int(lib().fd_ed25519_amd_workspace_footprint(int(n)))
+
+
+WS_PLANES = ("dig", "evn", "top", "A", "R", "Ai", "st", "tag", "ds", "init", "ctr")   # FD_ED25519_AMD_WS_DIG ..
+
+
+def debug_ws_layout(n):
+    """fd_ed25519_amd_debug_ws_layout (host only, no device): {"N": rows,
+    plane name: byte offset for each of WS_PLANES, "total": the footprint}
+    of an n-signature workspace."""
+    out = (ctypes.c_ulong * (len(WS_PLANES) + 2))()
+    lib().fd_ed25519_amd_debug_ws_layout(int(n), out)
+    return dict(zip(("N",) + WS_PLANES + ("total",), (int(v) for v in out)))
 
 
 def verify_dev(n, d_pub, d_sig, d_off, d_sz, d_blob, d_err, d_ws, stream=0, mode=MODE_REFERENCE):

@@ -440,7 +440,19 @@ fd_ed25519_amd_multi_verify_soa_tag( fd_ed25519_amd_multi_t * multi,
    resident (the layout of fd_ed25519_amd_verify_soa).  Enqueues the
    verify kernels on `stream` (hipStream_t, NULL = default stream) and
    returns without synchronising.  `ws` is device scratch of at least
-   fd_ed25519_amd_workspace_footprint(n) bytes, 256-aligned. */
+   fd_ed25519_amd_workspace_footprint(n) bytes, 256-aligned.
+
+   Contract on memory (tests/test_workspace_state_gpu.py; the plane table
+   is in DESIGN.md s2): the workspace may hold anything on entry -- the
+   leftovers of a launch with another n, kernel or mode, or arbitrary bytes
+   -- and no result depends on it: every plane element a kernel reads was
+   written earlier in the same call.  The call writes ws[0, footprint(n)),
+   d_err[0, n) -- every entry, whatever it held -- and nothing else; the
+   input planes (d_pub, d_sig, d_msg_off, d_msg_sz, d_blob) are only read.
+   The read-back calls below (work_stats, tags, debug_*) write the n
+   entries of their named output and nothing else, and do not write the
+   workspace.  One workspace serves one call at a time; calls in flight on
+   different streams need workspaces of their own. */
 ulong
 fd_ed25519_amd_workspace_footprint( ulong n );
 
@@ -621,6 +633,31 @@ fd_ed25519_amd_debug_set_pool_waves( ulong w );
 #define FD_ED25519_AMD_DSM_K_DSMP  (4)
 int
 fd_ed25519_amd_debug_rprime_dev( ulong n, void const * d_ws, int kind, int * d_xyz, void * stream );
+
+/* Debug: where the planes of an n-signature workspace lie (pure host code,
+   no device): out[0] = N, the row count (n rounded up to 64, at least 64);
+   out[1..11] = the byte offsets of the planes dig, evn, top, A, R, Ai, st,
+   tag, ds, init, ctr, in this order; out[12] =
+   fd_ed25519_amd_workspace_footprint( n ).  The FD_ED25519_AMD_WS_* names
+   index out.  Plane sizes in bytes: dig 256 N, evn 4 N, top 4 N, A 120 N,
+   R 80 N, Ai 1536 N, st 12 N, tag 8 N, ds 2 N, init 16 N, ctr 16; every
+   offset is a multiple of 256.  out == NULL does nothing. */
+#define FD_ED25519_AMD_WS_N          (0)
+#define FD_ED25519_AMD_WS_DIG        (1)
+#define FD_ED25519_AMD_WS_EVN        (2)
+#define FD_ED25519_AMD_WS_TOP        (3)
+#define FD_ED25519_AMD_WS_A          (4)
+#define FD_ED25519_AMD_WS_R          (5)
+#define FD_ED25519_AMD_WS_AI         (6)
+#define FD_ED25519_AMD_WS_ST         (7)
+#define FD_ED25519_AMD_WS_TAG        (8)
+#define FD_ED25519_AMD_WS_DS         (9)
+#define FD_ED25519_AMD_WS_INIT       (10)
+#define FD_ED25519_AMD_WS_CTR        (11)
+#define FD_ED25519_AMD_WS_TOTAL      (12)
+#define FD_ED25519_AMD_WS_LAYOUT_CNT (13)
+void
+fd_ed25519_amd_debug_ws_layout( ulong n, ulong * out );
 
 /* Library version / build string. */
 char const *

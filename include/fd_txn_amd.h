@@ -323,7 +323,17 @@ fd_ed25519_amd_txn_gather_layout( ulong         n,
    fd_ed25519_amd_txn_workspace_footprint(txn_cnt, slot_cnt) bytes,
    256-aligned; it begins with the signature verify's workspace, so
    fd_ed25519_amd_work_stats_dev( slot_cnt, d_ws, ... ) reads the call's
-   per-signature work statistics. */
+   per-signature work statistics.
+
+   Contract on memory, as for fd_ed25519_amd_verify_dev: d_ws may hold
+   anything on entry -- for instance the slots of an earlier batch, each
+   with a signature that verified -- and no result depends on it: the parse
+   kernel marks or fills every slot of [0, slot_cnt) (d_tbase must cover
+   them: d_tbase[0] = 0, ascending), and a slot of a payload that did not
+   parse is never verified, whatever it holds.  The call writes
+   d_ws[0, footprint), d_txn_err[0, txn_cnt), d_sig_err[0, slot_cnt) --
+   every entry -- and nothing else; d_payload, d_txn_off, d_txn_sz and
+   d_tbase are only read. */
 ulong
 fd_ed25519_amd_txn_workspace_footprint( ulong txn_cnt, ulong slot_cnt );
 
