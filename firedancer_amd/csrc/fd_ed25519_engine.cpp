@@ -68,6 +68,8 @@ slot_free( slot_t * s ) {
   if( s->h_tbase) (void)hipHostFree( s->h_tbase );
   if( s->h_terr ) (void)hipHostFree( s->h_terr );
   if( s->h_tag  ) (void)hipHostFree( s->h_tag );
+  if( s->d_dpack) (void)hipFree( s->d_dpack );
+  if( s->h_dpack) (void)hipHostFree( s->h_dpack );
   if( s->stream ) (void)hipStreamDestroy( s->stream );
   if( s->done   ) (void)hipEventDestroy( s->done );
   memset( s, 0, sizeof(*s) );
@@ -170,6 +172,33 @@ slot_alloc_tag( slot_t * s, ulong cap ) {
   return FD_ED25519_AMD_OK;
 }
 
+/* A chunk's worst case of packed descriptor bytes: every transaction at most
+   FD_TXN_MAX_SZ (payloads are <= FD_TXN_AMD_MTU here), and by
+   fd_txn_amd_desc_bound at most 20 + 10*sz/3 each with the sizes summing to
+   at most blob_cap.  A multiple of 256. */
+static ulong
+desc_stage_sz( ulong cap, ulong blob_cap ) {
+  ulong a = FD_TXN_MAX_SZ*cap, b = 20UL*cap + 10UL*blob_cap/3UL;
+  return ( ( a < b ? a : b ) + 255UL ) & ~255UL;
+}
+
+/* The slot's descriptor staging, on the first chunk whose caller asked for
+   descriptors. */
+static int
+slot_alloc_desc( slot_t * s, ulong cap, ulong blob_cap ) {
+  if( s->d_dpack ) return FD_ED25519_AMD_OK;
+  ulong const stage = desc_stage_sz( cap, blob_cap );
+  ulong const off_sz = ( 8UL*(cap+1UL) + 255UL ) & ~255UL, bs_sz = ( 8UL*((cap+63UL)/64UL) + 255UL ) & ~255UL;
+  HIPCHK( hipMalloc( (void **)&s->d_dpack, off_sz + bs_sz + stage ) );
+  s->d_doff = (ulong *)s->d_dpack; s->d_dbsum = (ulong *)(s->d_dpack + off_sz); s->d_desc = s->d_dpack + off_sz + bs_sz;
+  HIPCHK( hipHostMalloc( (void **)&s->h_dpack, off_sz + stage, hipHostMallocMapped | hipHostMallocCoherent ) );
+  s->h_doff = (ulong *)s->h_dpack; s->h_desc = s->h_dpack + off_sz;
+  HIPCHK( hipHostGetDevicePointer( &s->m_doff, s->h_dpack, 0 ) );
+  s->m_desc = (uint8_t *)s->m_doff + off_sz;
+  s->desc_stage = stage;
+  return FD_ED25519_AMD_OK;
+}
+
 /* The n tags of the chunk just verified on s (the tag plane of its
    workspace) into h_tag, on the slot's stream: k_tag_out writes the mapped
    buffer, on every path, as slot_out does the verdicts and for its reason.
@@ -193,15 +222,28 @@ slot_drain( slot_t * s ) {
   bool fault = ( s->chk_err  && s->h_err[0] == (int8_t)FD_AMD_VERDICT_DEVICE ) ||
                ( s->chk_terr && memchr( s->h_terr, (uint8_t)FD_AMD_VERDICT_DEVICE, s->chk_terr ) );
   if( fault ) fprintf( stderr, "fd_ed25519_amd: the pooled double-scalar multiply hit its step guard\n" );
-  else {
+  /* descriptors: the chunk's total is known only now.  The callers' bound
+     check keeps both conditions from ever holding; they are the backstop that
+     keeps the copy below inside the staging and the caller's buffer */
+  else if( s->do_out && ( s->h_doff[s->do_n] > s->desc_stage || *s->d_base + s->h_doff[s->do_n] > s->d_cap ) ) {
+    fprintf( stderr, "fd_ed25519_amd: a chunk's descriptors exceed their bound\n" );
+    fault = true;
+  } else {
     if( s->out   ) memcpy( s->out,   s->h_err,  s->n );
     if( s->t_out ) memcpy( s->t_out, s->h_terr, s->t_n );
     if( s->s_out ) memcpy( s->s_out, s->h_err,  s->s_n );
     if( s->g_out  ) memcpy( s->g_out,  s->h_tag,  8UL*s->g_n );
     if( s->tg_out ) memcpy( s->tg_out, s->h_ttag, 8UL*s->tg_n );
+    if( s->do_out ) {   /* chunk-relative offsets -> the batch's numbering; the bytes behind the earlier chunks' */
+      ulong const base = *s->d_base, tot = s->h_doff[s->do_n];
+      for( ulong j=0; j<=s->do_n; j++ ) s->do_out[j] = base + s->h_doff[j];
+      if( tot ) memcpy( s->d_out + base, s->h_desc, tot );
+      *s->d_base = base + tot;
+    }
   }
   s->out = s->t_out = s->s_out = NULL;
   s->g_out = s->tg_out = NULL;
+  s->do_out = NULL;
   s->busy = 0;
   return fault ? FD_ED25519_AMD_ERR_DEVICE : FD_ED25519_AMD_OK;
 }
@@ -216,6 +258,7 @@ engine_quiesce( fd_ed25519_amd_t * e, int rc ) {
     if( s->busy ) (void)hipEventSynchronize( s->done );
     s->out = s->t_out = s->s_out = NULL;
     s->g_out = s->tg_out = NULL;
+    s->do_out = NULL;
     s->busy = 0;
   }
   return rc;
@@ -263,24 +306,28 @@ slot_launch_packed( slot_t * s, ulong n, ulong blob_sz, schar * out, ulong * tag
    h_tbase[0..c]), nslot = h_tbase[c] signature slots.  Per-transaction
    verdicts land in h_terr, per-signature ones (when s_out) in h_err; the
    per-transaction tags (when tt_out) in h_ttag, the per-signature ones (when
-   st_out) in h_tag. */
-static int slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, schar * t_out, schar * s_out, ulong * tt_out, ulong * st_out );
+   st_out) in h_tag; with dq != NULL the chunk's descriptors, packed, in
+   h_desc and their chunk-relative offsets in h_doff[0..c]. */
+static int slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, schar * t_out, schar * s_out, ulong * tt_out, ulong * st_out,
+                                desc_req_t const * dq );
 
 static int
 slot_launch_txn( slot_t * s, ulong c, ulong nslot, ulong blob_sz, schar * t_out, schar * s_out, ulong * tt_out,
-                 ulong * st_out ) {
+                 ulong * st_out, desc_req_t const * dq ) {
   HIPCHK( hipMemcpyAsync( s->d_toff,  s->h_toff,  4UL*c,        hipMemcpyHostToDevice, s->stream ) );
   HIPCHK( hipMemcpyAsync( s->d_tsz,   s->h_tsz,   4UL*c,        hipMemcpyHostToDevice, s->stream ) );
   HIPCHK( hipMemcpyAsync( s->d_tbase, s->h_tbase, 4UL*(c+1UL),  hipMemcpyHostToDevice, s->stream ) );
   if( blob_sz ) HIPCHK( hipMemcpyAsync( s->d_blob, s->h_blob, blob_sz, hipMemcpyHostToDevice, s->stream ) );
-  return slot_launch_txn_dev( s, c, nslot, t_out, s_out, tt_out, st_out );
+  return slot_launch_txn_dev( s, c, nslot, t_out, s_out, tt_out, st_out, dq );
 }
 
 /* The kernels of a transaction chunk whose payloads and planes (d_blob,
    d_toff, d_tsz, d_tbase[0..c]) are on the device, or on their way there on
-   the slot's stream: parse, verify with d_skip, reduce, outputs, tags. */
+   the slot's stream: parse, verify with d_skip, reduce, outputs, tags,
+   descriptors. */
 static int
-slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, schar * t_out, schar * s_out, ulong * tt_out, ulong * st_out ) {
+slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, schar * t_out, schar * s_out, ulong * tt_out, ulong * st_out,
+                     desc_req_t const * dq ) {
   if( fd_amd_launch_txn_parse( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, s->d_fp, NULL, 0, s->d_tbase,
                                s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_skip, s->stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
@@ -295,7 +342,19 @@ slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, schar * t_out, schar * s_
   /* tags: per transaction its first slot's (no slot launched: no workspace is read), per signature the plane */
   if( tt_out && fd_amd_launch_tag_gather( s->m_ttag, s->d_ws, (uint32_t)c, s->d_tbase, s->stream ) ) return FD_ED25519_AMD_ERR_DEVICE;
   if( st_out && nslot && slot_tags( s, nslot ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  /* descriptors: packed in HBM from the footprints k_txn_parse left (0 where
+     it rejected the payload, the fail-closed slot mismatch included), then
+     one coalesced copy-out that reads the chunk's total on the device: the
+     host learns it from h_doff[c] when it drains the slot, without a sync */
+  if( dq ) {
+    if( fd_amd_launch_txn_pack( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, s->d_fp, s->d_dbsum, s->d_doff, s->d_desc,
+                                s->desc_stage, s->stream ) ||
+        fd_amd_launch_desc_out( s->m_desc, s->d_desc, s->m_doff, s->d_doff, (uint32_t)c, s->desc_stage, dq->bound, s->stream ) )
+      return FD_ED25519_AMD_ERR_DEVICE;
+  }
   HIPCHK( hipEventRecord( s->done, s->stream ) );
+  s->do_out = dq ? dq->off : NULL; s->do_n = c;
+  if( dq ) { s->d_out = dq->desc; s->d_cap = dq->cap; s->d_base = dq->base; }
   s->tg_out = tt_out; s->tg_n = c;
   s->g_out = nslot ? st_out : NULL; s->g_n = nslot;
   s->t_out = t_out; s->t_n = c;
@@ -310,8 +369,8 @@ slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, schar * t_out, schar * s_
    chunk is drained before the slot is reused; stage( slot, first ) sizes,
    stages and launches the chunk that starts at item `first` and returns the
    items it took (> 0; the callers' argument checks see to that) or an error
-   code (< 0); the ring is drained at the end.  Any error quiesces the
-   engine. */
+   code (< 0); the ring is drained at the end, in the order the chunks were
+   launched, as the loop drains them.  Any error quiesces the engine. */
 template<typename STAGE>
 static int
 run_ring( fd_ed25519_amd_t * e, int ring, ulong total, STAGE stage ) {
@@ -324,7 +383,9 @@ run_ring( fd_ed25519_amd_t * e, int ring, ulong total, STAGE stage ) {
     if( c < 0L ) return engine_quiesce( e, (int)c );
     i += (ulong)c;
   }
-  for( int j=0; j<ring; j++ ) if( (rc = slot_drain( &e->slot[j] )) ) return engine_quiesce( e, rc );
+  /* oldest chunk first: slot k is the one the next chunk would have reused
+     (a chunk's descriptors are placed behind those of every earlier chunk) */
+  for( int j=0; j<ring; j++ ) if( (rc = slot_drain( &e->slot[(k + j) % ring] )) ) return engine_quiesce( e, rc );
   return FD_ED25519_AMD_OK;
 }
 
@@ -776,27 +837,63 @@ extern "C" int
 fd_ed25519_amd_verify_txns_tag( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
                                 uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                                 ulong * txn_tag, ulong * sig_tag ) {
+  return fd_ed25519_amd_verify_txns_desc( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err,
+                                          txn_tag, sig_tag, NULL, NULL, 0UL );
+}
+
+/* How big a descriptor can be.  A payload that parses holds at least one
+   signature count byte, one 64-B signature, three header bytes, the account
+   count, one 32-B account address, the 32-B blockhash and the instruction
+   count: 1 + 64 + 3 + 1 + 32 + 32 + 1 = 134 bytes (a v0 payload two more).
+   Behind them every instruction takes at least 3 payload bytes (program
+   index and two counts) for its 10 descriptor bytes, and every lookup table
+   at least 34 (address and two counts) for its 8.  With i instructions and l
+   tables, 3 i + 34 l <= sz - 134, so i + 11 l <= (sz - 134)/3 rounded down,
+   and the footprint 20 + 10 i + 8 l <= 20 + 10 (i + 11 l).  Up to the MTU no
+   footprint exceeds FD_TXN_MAX_SZ (fd_txn.h:88-95). */
+extern "C" ulong
+fd_txn_amd_desc_bound( ulong payload_sz ) {
+  if( payload_sz < 134UL || payload_sz > FD_TXN_AMD_PAYLOAD_MAX ) return 0UL;
+  ulong b = 20UL + 10UL*( ( payload_sz - 134UL )/3UL );
+  return ( payload_sz <= FD_TXN_AMD_MTU && b > FD_TXN_MAX_SZ ) ? FD_TXN_MAX_SZ : b;
+}
+
+extern "C" int
+fd_ed25519_amd_verify_txns_desc( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
+                                 uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                                 ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap ) {
   int rc = fd_amd_txn_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag );
   if( rc ) return rc;
+  if( !desc != !desc_off ) return FD_ED25519_AMD_ERR_INVAL;
+  if( desc_off ) {   /* capacity is decided by the bound, never by the data */
+    ulong need = 0;
+    for( ulong t=0; t<txn_cnt; t++ ) need += fd_txn_amd_desc_bound( txn_sz[t] );
+    if( desc_cap < need ) return FD_ED25519_AMD_ERR_INVAL;
+    desc_off[0] = 0UL;
+  }
+  ulong dbase = 0;   /* descriptor bytes of the chunks delivered so far */
   /* global signature numbering (the caller-visible sig_base) */
   if( sig_base ) fd_ed25519_amd_txn_slots( txn_cnt, payload, txn_off, txn_sz, sig_base );
   ulong gsig = 0;
   return run_ring( e, 2, txn_cnt, [&]( slot_t * s, ulong t ) -> long {
     int rc = slot_alloc_aux( s, e->cap );
     if( !rc && (txn_tag || sig_tag) ) rc = slot_alloc_tag( s, e->cap );
+    if( !rc && desc_off ) rc = slot_alloc_desc( s, e->cap, e->blob_cap );
     if( rc ) return rc;
     ulong c = 0, bsz = 0, ns = 0;
+    desc_req_t dq = { desc_off ? desc_off + t : NULL, desc, desc_cap, &dbase, 0UL };
     while( t + c < txn_cnt && c < e->cap ) {
       uchar const * p = payload + txn_off[t+c];
       ulong sz = txn_sz[t+c], k2 = fd_amd_txn_slots1( p, sz );
       if( bsz + sz > e->blob_cap || ns + k2 > e->cap ) break;
       if( sz ) memcpy( s->h_blob + bsz, p, sz );
       s->h_toff[c] = (uint32_t)bsz; s->h_tsz[c] = (uint32_t)sz; s->h_tbase[c] = (uint32_t)ns;
+      if( desc_off ) dq.bound += fd_txn_amd_desc_bound( sz );
       bsz += sz; ns += k2; c++;
     }
     s->h_tbase[c] = (uint32_t)ns;
     rc = slot_launch_txn( s, c, ns, bsz, txn_err + t, sig_err ? sig_err + gsig : NULL, txn_tag ? txn_tag + t : NULL,
-                          sig_tag ? sig_tag + gsig : NULL );
+                          sig_tag ? sig_tag + gsig : NULL, desc_off ? &dq : NULL );
     gsig += ns;
     return rc ? rc : (long)c;
   } );
@@ -843,7 +940,7 @@ fd_ed25519_amd_txn_gather_layout( ulong n, ulong const * sz, uint const * slots,
    slot_launch_gather's do. */
 static int
 slot_launch_txn_gather( slot_t * s, ulong c, ulong nslot, uint waves, schar * t_out, schar * s_out, ulong * tt_out,
-                        ulong * st_out ) {
+                        ulong * st_out, desc_req_t const * dq ) {
   /* A throughput chunk's gather runs beside the other slots' verify kernels
      and its reads of host memory hold up their memory traffic
      (slot_launch_gather): capped at `waves` waves, 64 unless
@@ -854,7 +951,7 @@ slot_launch_txn_gather( slot_t * s, ulong c, ulong nslot, uint waves, schar * t_
   if( fd_amd_launch_gather_txn( (uint32_t)c, (fd_amd_gather_txn_rec_t const *)s->m_pack, s->d_blob, s->d_toff, s->d_tsz,
                                 s->d_tbase, (uint32_t)nslot, lat ? 0u : waves, s->stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
-  return slot_launch_txn_dev( s, c, nslot, t_out, s_out, tt_out, st_out );
+  return slot_launch_txn_dev( s, c, nslot, t_out, s_out, tt_out, st_out, dq );
 }
 
 extern "C" int
@@ -867,10 +964,25 @@ extern "C" int
 fd_ed25519_amd_verify_txns_registered_tag( fd_ed25519_amd_t * e, ulong txn_cnt, void const * const * txn,
                                            ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                                            ulong * txn_tag, ulong * sig_tag ) {
+  return fd_ed25519_amd_verify_txns_registered_desc( e, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, txn_tag, sig_tag,
+                                                     NULL, NULL, 0UL );
+}
+
+extern "C" int
+fd_ed25519_amd_verify_txns_registered_desc( fd_ed25519_amd_t * e, ulong txn_cnt, void const * const * txn,
+                                            ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                                            ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc,
+                                            ulong desc_cap ) {
   if( !e || (txn_cnt && (!txn || !txn_sz || !txn_err)) ) return FD_ED25519_AMD_ERR_INVAL;
   if( (sig_err || sig_tag) && !sig_base ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !desc != !desc_off ) return FD_ED25519_AMD_ERR_INVAL;
   if( txn_cnt > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
-  if( !txn_cnt ) { if( sig_base ) sig_base[0] = 0U; return FD_ED25519_AMD_OK; }
+  if( !txn_cnt ) { if( sig_base ) sig_base[0] = 0U; if( desc_off ) desc_off[0] = 0UL; return FD_ED25519_AMD_OK; }
+  if( desc_off ) {   /* capacity is decided by the bound, never by the data */
+    ulong need = 0;
+    for( ulong t=0; t<txn_cnt; t++ ) need += fd_txn_amd_desc_bound( txn_sz[t] );
+    if( desc_cap < need ) return FD_ED25519_AMD_ERR_INVAL;
+  }
   reg_view_t view;
   /* every transaction before anything launches: its pointer, its size, its
      first and last byte in one registration of the table, and the signature
@@ -903,6 +1015,7 @@ fd_ed25519_amd_verify_txns_registered_tag( fd_ed25519_amd_t * e, ulong txn_cnt, 
     for( int t=1; t<nt; t++ ) th[t-1].join();
     for( int t=0; t<nt; t++ ) if( !ok[t] ) return FD_ED25519_AMD_ERR_INVAL;
   }
+  if( desc_off ) desc_off[0] = 0UL;
   /* global signature numbering (the caller-visible sig_base) */
   if( sig_base ) {
     ulong acc = 0;
@@ -910,10 +1023,13 @@ fd_ed25519_amd_verify_txns_registered_tag( fd_ed25519_amd_t * e, ulong txn_cnt, 
     sig_base[txn_cnt] = (uint)acc;
   }
   ulong gsig = 0;
+  ulong dbase = 0;   /* descriptor bytes of the chunks delivered so far */
   return run_ring( e, e->nslot, txn_cnt, [&]( slot_t * s, ulong t ) -> long {
     int rc = slot_alloc_aux( s, e->cap );
     if( !rc && (txn_tag || sig_tag) ) rc = slot_alloc_tag( s, e->cap );
+    if( !rc && desc_off ) rc = slot_alloc_desc( s, e->cap, e->blob_cap );
     if( rc ) return rc;
+    desc_req_t dq = { desc_off ? desc_off + t : NULL, desc, desc_cap, &dbase, 0UL };
     /* the chunk's records in h_pack (32 B per transaction), their dst behind them */
     fd_amd_gather_txn_rec_t * rec = (fd_amd_gather_txn_rec_t *)s->h_pack;
     uint * dst = (uint *)(s->h_pack + 32UL*e->cap);
@@ -928,10 +1044,11 @@ fd_ed25519_amd_verify_txns_registered_tag( fd_ed25519_amd_t * e, ulong txn_cnt, 
       if( sz > FD_TXN_AMD_MTU || sz > e->blob_cap || ( sz && ( !txn[t+j] || !view.xlat( txn[t+j], sz, &rec[j].src ) ) ) )
         return FD_ED25519_AMD_ERR_INVAL;
       rec[j].sz = (uint32_t)sz; rec[j].dst = dst[j]; rec[j].tbase = (uint32_t)b;
+      if( desc_off ) dq.bound += fd_txn_amd_desc_bound( sz );
       b += slots[t+j];
     }
     rc = slot_launch_txn_gather( s, c, ns, (uint)e->gather_txn_waves, txn_err + t, sig_err ? sig_err + gsig : NULL,
-                                 txn_tag ? txn_tag + t : NULL, sig_tag ? sig_tag + gsig : NULL );
+                                 txn_tag ? txn_tag + t : NULL, sig_tag ? sig_tag + gsig : NULL, desc_off ? &dq : NULL );
     gsig += ns;
     return rc ? rc : (long)c;
   } );
@@ -1014,6 +1131,29 @@ fd_txn_amd_parse_dev( ulong txn_cnt, uchar const * d_payload, uint const * d_txn
   if( d_out && (out_stride < FD_TXN_MAX_SZ || (out_stride & 1UL)) ) return FD_ED25519_AMD_ERR_INVAL;
   if( fd_amd_launch_txn_parse( (uint32_t)txn_cnt, d_payload, d_txn_off, d_txn_sz, d_footprint, d_out, out_stride,
                                NULL, NULL, NULL, NULL, NULL, NULL, (hipStream_t)stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" ulong
+fd_txn_amd_parse_packed_scratch_footprint( ulong txn_cnt ) {
+  ulong nblk = ( txn_cnt + 63UL )/64UL;   /* one 64-bit total per 64 transactions */
+  return al256( 8UL*( nblk ? nblk : 1UL ) );
+}
+
+extern "C" int
+fd_txn_amd_parse_packed_dev( ulong txn_cnt, uchar const * d_payload, uint const * d_txn_off, uint const * d_txn_sz,
+                             uint * d_footprint, ulong * d_desc_off, uchar * d_desc, ulong desc_cap, void * d_scratch,
+                             void * stream ) {
+  if( txn_cnt > 0xFFFFFFFFUL || !d_desc_off ) return FD_ED25519_AMD_ERR_INVAL;
+  if( txn_cnt && ( !d_payload || !d_txn_off || !d_txn_sz || !d_footprint || !d_scratch ) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( ( desc_cap && !d_desc ) || ( (ulong)d_desc & 1UL ) || ( (ulong)d_desc_off & 7UL ) || ( (ulong)d_scratch & 7UL ) )
+    return FD_ED25519_AMD_ERR_INVAL;
+  /* footprint pass: the validate-only parse; then the scan and the store pass */
+  if( fd_amd_launch_txn_parse( (uint32_t)txn_cnt, d_payload, d_txn_off, d_txn_sz, d_footprint, NULL, 0, NULL, NULL, NULL,
+                               NULL, NULL, NULL, (hipStream_t)stream ) ||
+      fd_amd_launch_txn_pack( (uint32_t)txn_cnt, d_payload, d_txn_off, d_txn_sz, d_footprint, (uint64_t *)d_scratch,
+                              (uint64_t *)d_desc_off, d_desc, desc_cap, (hipStream_t)stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
   return FD_ED25519_AMD_OK;
 }

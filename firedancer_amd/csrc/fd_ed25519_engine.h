@@ -46,6 +46,31 @@ struct slot_t {
   /* tags of the chunk in flight (NULL: not asked for): g_n from h_tag, tg_n from h_ttag */
   ulong * g_out;  ulong g_n;
   ulong * tg_out; ulong tg_n;
+  /* packed descriptors (allocated by the first call that asks for them).
+     d_dpack, one device allocation: d_doff[cap+1], the chunk-relative 64-bit
+     offsets; d_dbsum, the scan's block totals; d_desc[desc_stage], the packed
+     bytes.  h_dpack, one mapped pinned allocation written by k_desc_out:
+     h_doff[cap+1] and h_desc[desc_stage] (m_doff / m_desc: their device
+     addresses).  desc_stage: a chunk's worst case, a multiple of 256. */
+  uint8_t * d_dpack; ulong * d_doff; ulong * d_dbsum; uint8_t * d_desc;
+  uint8_t * h_dpack; ulong * h_doff; uint8_t * h_desc;
+  void    * m_doff;  void  * m_desc;
+  ulong     desc_stage;
+  /* descriptors of the chunk in flight (do_out NULL: not asked for): on
+     delivery do_out[0 .. do_n] = *d_base + h_doff[..], the h_doff[do_n] bytes
+     go to d_out + *d_base (d_cap: the caller's capacity) and *d_base grows
+     by them -- so chunks must be drained in the order they were launched */
+  ulong * do_out; ulong do_n;
+  uchar * d_out;  ulong d_cap;
+  ulong * d_base;
+};
+
+/* What a transaction chunk's launch needs to return descriptors: where the
+   chunk's offsets go (its first transaction's entry of the caller's
+   desc_off), the caller's buffer and capacity, the call's running byte base,
+   and the chunk's bound (the sum of fd_txn_amd_desc_bound over it). */
+struct desc_req_t {
+  ulong * off; uchar * desc; ulong cap; ulong * base; ulong bound;
 };
 
 #define FD_AMD_SLOT_MAX (16)

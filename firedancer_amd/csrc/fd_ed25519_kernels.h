@@ -57,6 +57,26 @@ int fd_amd_launch_txn_parse( uint32_t txn_cnt, uint8_t const * d_payload, uint32
 int fd_amd_launch_txn_reduce( uint32_t txn_cnt, uint32_t const * d_fp, uint32_t const * d_tbase,
                               int8_t const * d_err, int8_t * d_terr, hipStream_t stream );
 
+/* Packed descriptors (fd_txn_kernels.hip), after a k_txn_parse that left
+   d_fp: d_desc_off[0 .. txn_cnt] = the 64-bit exclusive prefix sum of d_fp
+   (d_desc_off[txn_cnt] the total) and, for every t with d_fp[t] != 0 and
+   d_desc_off[t+1] <= desc_cap, the descriptor at d_desc + d_desc_off[t]
+   (d_desc 2-aligned); no byte at or beyond d_desc + desc_cap is written.
+   d_bsum: scratch, one u64 per 64 transactions.  Three kernels ordered by
+   the stream (txn_cnt == 0: the one that writes d_desc_off[0]); no workgroup
+   waits for another.
+   fd_amd_launch_desc_out: d_desc_off[0 .. txn_cnt] and the first
+   min( d_desc_off[txn_cnt], cap ) packed bytes, rounded up to 16, to mapped
+   host memory by a kernel that reads the total on the device; all four
+   buffers are 16-aligned and the byte buffers hold round_up( cap, 16 )
+   bytes.  bound: what
+   the host knows the total cannot exceed (sizes the grid only). */
+int fd_amd_launch_txn_pack( uint32_t txn_cnt, uint8_t const * d_payload, uint32_t const * d_toff, uint32_t const * d_tsz,
+                            uint32_t const * d_fp, uint64_t * d_bsum, uint64_t * d_desc_off, uint8_t * d_desc,
+                            uint64_t desc_cap, hipStream_t stream );
+int fd_amd_launch_desc_out( void * d_dst_mapped, uint8_t const * d_desc, void * d_off_mapped, uint64_t const * d_desc_off,
+                            uint32_t txn_cnt, uint64_t cap, uint64_t bound, hipStream_t stream );
+
 /* GPU keygen + sign (fd_ed25519_sign.hip): prv[n][32] seeds, messages
    blob[off[i] .. +sz[i]) -> pub[n][32], sig[n][64].  0 on success. */
 int fd_amd_launch_sign( uint32_t n, uint8_t const * d_prv, uint32_t const * d_off, uint32_t const * d_sz,

@@ -177,6 +177,41 @@ txn_parse( u8 const * payload, u32 sz, u8 * o, u32 ocap, u32 * nsig_out, u32 * s
   return (u32)TX_HDR + IX_SZ*ninstr + LUT_SZ*nlut;                     /* fd_txn_footprint */
 }
 
+/* ---- packed descriptors (fd_txn_kernels.hip: k_desc_bsum, k_desc_bscan,
+   k_desc_store) ----
+
+   Descriptor t of a batch goes to desc + off[t], off = the exclusive prefix
+   sum of the footprints (0 for a rejected payload), carried in 64 bits.  The
+   sum is made in three stream-ordered steps and no workgroup ever waits for
+   another: per 64-transaction block its footprint total (k_desc_bsum), one
+   64-lane workgroup that scans the block totals, looping 64 at a time with a
+   64-bit carry (k_desc_bscan), and per block again the in-wave scan on top
+   of the block's base (k_desc_store).  The in-wave sums stay in 32 bits:
+   64 footprints of at most 220502 are < 2^24, 64 block totals < 2^30. */
+
+#define TXN_PACK_BLOCK 64u   /* transactions per block of the scan = lanes per workgroup */
+
+/* inclusive sum over the wave's 64 lanes; every lane of the wave calls it */
+__device__ __forceinline__ u32
+wave_scan_incl( u32 v, u32 lane ) {
+  for( u32 d=1u; d<64u; d<<=1 ) {
+    u32 up = (u32)__shfl_up( (int)v, d, 64 );
+    if( lane >= d ) v += up;
+  }
+  return v;
+}
+
+/* Store pass for one accepted transaction: walk the payload again, this
+   time with its final destination.  fp is the footprint the first pass
+   returned and bounds every store (txn_parse stores a record only if it ends
+   at or before ocap = fp, the 20-B header fits any fp > 0), so the lane
+   writes [o, o + fp) and nothing else even if the payload changed since. */
+__device__ __forceinline__ void
+txn_desc_store( u8 const * payload, u32 sz, u8 * o, u32 fp ) {
+  u32 nsig = 0u, sig_off = 0u, acct_off = 0u, msg_off = 0u;
+  (void)txn_parse( payload, sz, o, fp, &nsig, &sig_off, &acct_off, &msg_off );
+}
+
 } /* namespace fd_txn_dev */
 
 #endif /* FD_TXN_DEV_H */

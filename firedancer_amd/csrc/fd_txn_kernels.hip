@@ -13,6 +13,11 @@
  *   k_txn_parse   parse + signature layout (one lane per transaction)
  *   k_txn_reduce  per-transaction verdict: parse failure, else the first
  *                 failing signature's code in signature order, else 0
+ *   k_desc_bsum, k_desc_bscan, k_desc_store
+ *                 packed descriptors: a 64-bit exclusive scan of the
+ *                 footprints and a second walk of the accepted payloads
+ *                 that stores each descriptor at its offset
+ *   k_desc_out    a chunk's offsets and packed bytes to mapped host memory
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,6 +26,7 @@
 typedef uint8_t  u8;
 typedef uint16_t u16;
 typedef uint32_t u32;
+typedef uint64_t u64;
 typedef int8_t   i8;
 
 #include "fd_txn_dev.h"
@@ -85,6 +91,91 @@ k_txn_reduce( u32 txn_cnt, u32 const * __restrict__ fp, u32 const * __restrict__
   i8 r = 0;
   for( u32 s=tbase[t]; s<tbase[t+1u]; s++ ) { i8 e = err[s]; if( e ) { r = e; break; } }
   terr[t] = r;
+}
+
+/* Packed descriptors (fd_txn_dev.h, "packed descriptors"): three kernels,
+   ordered by the stream alone. */
+
+/* bsum[b] = the footprint total of transactions [64 b, 64 b + 64) */
+__global__ void __launch_bounds__(64)
+k_desc_bsum( u32 txn_cnt, u32 const * __restrict__ fp, u64 * __restrict__ bsum ) {
+  u32 lane = threadIdx.x, t = blockIdx.x * TXN_PACK_BLOCK + lane;
+  u32 incl = wave_scan_incl( t < txn_cnt ? fp[t] : 0u, lane );
+  if( lane == 63u ) bsum[blockIdx.x] = (u64)incl;
+}
+
+/* One workgroup: bsum[0, nblk) becomes its own exclusive prefix sum, 64
+   entries per turn of the loop, and desc_off[txn_cnt] the grand total. */
+__global__ void __launch_bounds__(64)
+k_desc_bscan( u32 nblk, u64 * __restrict__ bsum, u64 * __restrict__ desc_off, u32 txn_cnt ) {
+  u32 lane = threadIdx.x;
+  u64 carry = 0UL;
+  for( u32 base=0u; base<nblk; base+=64u ) {          /* wave-uniform trip count */
+    u32 i = base + lane;
+    u32 v = i < nblk ? (u32)bsum[i] : 0u;
+    u32 incl = wave_scan_incl( v, lane );
+    if( i < nblk ) bsum[i] = carry + (u64)(incl - v);
+    carry += (u64)(u32)__shfl( (int)incl, 63, 64 );
+  }
+  if( lane == 0u ) desc_off[txn_cnt] = carry;
+}
+
+/* desc_off[t] for every transaction, and the descriptor of every accepted
+   one whose end is within cap */
+__global__ void __launch_bounds__(64)
+k_desc_store( u32 txn_cnt, u8 const * __restrict__ payload, u32 const * __restrict__ toff, u32 const * __restrict__ tsz,
+              u32 const * __restrict__ fp, u64 const * __restrict__ bsum, u64 * __restrict__ desc_off,
+              u8 * __restrict__ desc, u64 cap ) {
+  u32 lane = threadIdx.x, t = blockIdx.x * TXN_PACK_BLOCK + lane;
+  u32 f = t < txn_cnt ? fp[t] : 0u;
+  u32 incl = wave_scan_incl( f, lane );
+  if( t >= txn_cnt ) return;
+  u64 off = bsum[blockIdx.x] + (u64)(incl - f);
+  desc_off[t] = off;
+  if( f && off + (u64)f <= cap ) txn_desc_store( payload + toff[t], tsz[t], desc + off, f );
+}
+
+/* A chunk's offsets and packed bytes, device -> mapped host memory, 16 B per
+   lane: off[0 .. txn_cnt] and the first min( off[txn_cnt], cap ) bytes,
+   rounded up to 16 (all four buffers are 16-aligned, and the byte buffers
+   end on a multiple of 16 at or after cap).  The byte total is read from the scan's last element,
+   so the host need not know it when it launches this. */
+__global__ void __launch_bounds__(256)
+k_desc_out( u8 * __restrict__ dst, u8 const * __restrict__ src, u64 * __restrict__ dst_off, u64 const * __restrict__ src_off,
+            u32 txn_cnt, u64 cap ) {
+  size_t i = (size_t)blockIdx.x * 256u + threadIdx.x, stride = (size_t)gridDim.x * 256u;
+  u64 total = src_off[txn_cnt];
+  size_t nv = (size_t)( ( ( total < cap ? total : cap ) + 15UL ) >> 4 );
+  for( size_t k = i; k < nv; k += stride ) ((uint4 *)dst)[k] = ((uint4 const *)src)[k];
+  size_t no = (size_t)txn_cnt + 1u, np = no >> 1;      /* the offsets two to a lane, the odd one last */
+  for( size_t k = i; k < np; k += stride ) ((ulong2 *)dst_off)[k] = ((ulong2 const *)src_off)[k];
+  if( (no & 1u) && i == 0 ) dst_off[no - 1u] = src_off[no - 1u];
+}
+
+int
+fd_amd_launch_txn_pack( uint32_t txn_cnt, uint8_t const * d_payload, uint32_t const * d_toff, uint32_t const * d_tsz,
+                        uint32_t const * d_fp, uint64_t * d_bsum, uint64_t * d_desc_off, uint8_t * d_desc,
+                        uint64_t desc_cap, hipStream_t stream ) {
+  u32 nblk = (u32)( ( (u64)txn_cnt + TXN_PACK_BLOCK - 1UL ) / TXN_PACK_BLOCK );
+  if( nblk ) hipLaunchKernelGGL( k_desc_bsum, dim3(nblk), dim3(64), 0, stream, txn_cnt, d_fp, (u64 *)d_bsum );
+  hipLaunchKernelGGL( k_desc_bscan, dim3(1), dim3(64), 0, stream, nblk, (u64 *)d_bsum, (u64 *)d_desc_off, txn_cnt );
+  if( nblk ) hipLaunchKernelGGL( k_desc_store, dim3(nblk), dim3(64), 0, stream, txn_cnt, d_payload, d_toff, d_tsz, d_fp,
+                                 (u64 const *)d_bsum, (u64 *)d_desc_off, d_desc, (u64)desc_cap );
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int
+fd_amd_launch_desc_out( void * d_dst_mapped, uint8_t const * d_desc, void * d_off_mapped, uint64_t const * d_desc_off,
+                        uint32_t txn_cnt, uint64_t cap, uint64_t bound, hipStream_t stream ) {
+  /* the grid covers the larger of the offsets and the chunk's bound (the
+     real total is at most that), one 16-B word per lane and turn */
+  uint64_t words = ( ( bound < cap ? bound : cap ) + 15UL ) >> 4;
+  if( words < (uint64_t)txn_cnt + 1UL ) words = (uint64_t)txn_cnt + 1UL;
+  uint64_t nb = ( words + 255UL ) / 256UL;
+  if( nb > 1024UL ) nb = 1024UL;
+  hipLaunchKernelGGL( k_desc_out, dim3((unsigned)nb), dim3(256), 0, stream, (u8 *)d_dst_mapped, d_desc, (u64 *)d_off_mapped,
+                      (u64 const *)d_desc_off, txn_cnt, (u64)cap );
+  return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int

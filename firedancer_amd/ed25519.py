@@ -169,6 +169,12 @@ def lib():
            "fd_ed25519_amd_verify_txns_registered_tag": ([vp, ul, vp, vp, vp, vp, vp, vp, vp], i),
            "fd_ed25519_amd_txn_slots_ptrs": ([ul, vp, vp, vp], ul),
            "fd_ed25519_amd_txn_gather_layout": ([ul, vp, vp, ul, ul, vp, vp], ul),
+           # packed descriptors
+           "fd_txn_amd_desc_bound": ([ul], ul),
+           "fd_txn_amd_parse_packed_dev": ([ul, vp, vp, vp, vp, vp, vp, ul, vp, vp], i),
+           "fd_txn_amd_parse_packed_scratch_footprint": ([ul], ul),
+           "fd_ed25519_amd_verify_txns_desc": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp, vp, vp, ul], i),
+           "fd_ed25519_amd_verify_txns_registered_desc": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, ul], i),
            # the streaming tile's verdict mode
            "fd_verify_amd_tile_set_verdict_mode": ([vp, i], i), "fd_verify_amd_tile_verdict_mode": ([vp], i),
            # debug: k_dsmp's grid, the parked R'
@@ -424,23 +430,27 @@ class Engine:
         return self.verify_batch_ptrs(base + np.asarray(pub_off, np.uint64), base + np.asarray(sig_off, np.uint64),
                                       base + np.asarray(msg_off, np.uint64), msg_sz, want_tags=want_tags)
 
-    def verify_txns(self, payload, txn_off, txn_sz, want_sigs=False, want_tags=False):
+    def verify_txns(self, payload, txn_off, txn_sz, want_sigs=False, want_tags=False, want_desc=False):
         """Wire-format transaction batch (include/fd_txn_amd.h): parse on the
         GPU, verify every signature (multi-signer rule), one verdict per
         transaction in {0, -1, -2, -3, FD_TXN_AMD_ERR_PARSE}.  With
         want_sigs, also returns (sig_base, sig_err); with want_tags the
         tuple ends with (txn_tag, sig_tag): uint64 per transaction (its
         first signature's dedup tag, 0 where it did not parse) and per
-        signature slot (the numbering of sig_err / txn_slots)."""
-        return _verify_txns("fd_ed25519_amd_verify_txns", self._h, payload, txn_off, txn_sz, want_sigs, want_tags)
+        signature slot (the numbering of sig_err / txn_slots).  With
+        want_desc (fd_ed25519_amd_verify_txns_desc) the tuple ends with
+        (desc_off, desc): uint64[n+1] offsets and the uint8[desc_off[-1]]
+        packed fd_txn_t descriptors of the transactions that parse; the
+        buffer is sized with txn_desc_bound."""
+        return _verify_txns("fd_ed25519_amd_verify_txns", self._h, payload, txn_off, txn_sz, want_sigs, want_tags, want_desc)
 
-    def verify_txns_ptrs(self, txn_ptr, txn_sz, want_sigs=False, want_tags=False):
+    def verify_txns_ptrs(self, txn_ptr, txn_sz, want_sigs=False, want_tags=False, want_desc=False):
         """fd_ed25519_amd_verify_txns_registered: the transaction batch in
         pointer-array form with no host staging.  txn_ptr: uint64 array of
         host addresses (txn_sz[t] payload bytes behind each, any alignment),
         every non-empty range inside one host_register registration; the GPU
         fetches the payloads itself.  Returns what verify_txns returns for
-        the same payloads."""
+        the same payloads (want_desc: fd_ed25519_amd_verify_txns_registered_desc)."""
         tp = np.ascontiguousarray(txn_ptr, np.uint64)
         sz = np.ascontiguousarray(txn_sz, np.uint64)
         n = int(tp.size)
@@ -455,8 +465,15 @@ class Engine:
             serr = np.zeros(max(tot, 1), np.int8)
         args = (self._h, n, _ptr(tp), _ptr(sz), _ptr(terr), _ptr(base) if base is not None else None,
                 _ptr(serr) if want_sigs else None)
+        ttag = stag = None
         if want_tags:
             ttag, stag = np.zeros(max(n, 1), np.uint64), np.zeros(max(tot, 1), np.uint64)
+        if want_desc:
+            doff, desc = _desc_buffers(sz)
+            rc = lib().fd_ed25519_amd_verify_txns_registered_desc(*args, _ptr(ttag) if want_tags else None,
+                                                                  _ptr(stag) if want_tags else None, _ptr(doff), _ptr(desc),
+                                                                  int(desc.size))
+        elif want_tags:
             rc = lib().fd_ed25519_amd_verify_txns_registered_tag(*args, _ptr(ttag), _ptr(stag))
         else:
             rc = lib().fd_ed25519_amd_verify_txns_registered(*args)
@@ -467,15 +484,33 @@ class Engine:
             out += (base, serr[:int(base[-1])])
         if want_tags:
             out += (ttag[:n], stag[:int(base[-1])])
+        if want_desc:
+            out += (doff, desc[:int(doff[-1])])
         return out if len(out) > 1 else out[0]
 
-    def verify_txns_registered(self, arena, txn_off, txn_sz, want_sigs=False, want_tags=False):
+    def verify_txns_registered(self, arena, txn_off, txn_sz, want_sigs=False, want_tags=False, want_desc=False):
         """verify_txns_ptrs over one registered uint8 arena (host_register):
         transaction t is arena[txn_off[t] : + txn_sz[t]]."""
         assert arena.dtype == np.uint8 and arena.flags["C_CONTIGUOUS"]
         base = np.uint64(arena.ctypes.data)
         return self.verify_txns_ptrs(base + np.asarray(txn_off, np.uint64), txn_sz, want_sigs=want_sigs,
-                                     want_tags=want_tags)
+                                     want_tags=want_tags, want_desc=want_desc)
+
+
+def txn_desc_bound(sz):
+    """fd_txn_amd_desc_bound: an upper bound on the fd_txn_t footprint of any
+    payload of sz bytes (0 where no payload of that size parses; no device)."""
+    return int(lib().fd_txn_amd_desc_bound(int(sz)))
+
+
+def _desc_buffers(txn_sz):
+    """(desc_off, desc) for a batch with these payload sizes: desc holds the
+    sum of txn_desc_bound, the capacity the _desc calls ask for (at least one
+    byte: the calls take no NULL desc)."""
+    bound = lib().fd_txn_amd_desc_bound
+    by_sz = {int(z): int(bound(int(z))) for z in np.unique(txn_sz)}
+    cap = sum(by_sz[int(z)] for z in np.asarray(txn_sz).tolist())
+    return np.zeros(len(txn_sz) + 1, np.uint64), np.zeros(max(cap, 1), np.uint8)
 
 
 def txn_slots_ptrs(txn_ptr, txn_sz):
@@ -532,8 +567,9 @@ def txn_slots(payload, txn_off, txn_sz):
     return base, int(tot)
 
 
-def _verify_txns(name, h, payload, txn_off, txn_sz, want_sigs, want_tags=False):
-    """name: fd_ed25519_amd_verify_txns or the multi form; want_tags calls its _tag form."""
+def _verify_txns(name, h, payload, txn_off, txn_sz, want_sigs, want_tags=False, want_desc=False):
+    """name: fd_ed25519_amd_verify_txns or the multi form; want_tags calls its
+    _tag form, want_desc its _desc form (the single-device call only)."""
     payload = np.ascontiguousarray(payload, np.uint8)
     off = np.ascontiguousarray(txn_off, np.uint32)
     sz = np.ascontiguousarray(txn_sz, np.uint32)
@@ -548,8 +584,14 @@ def _verify_txns(name, h, payload, txn_off, txn_sz, want_sigs, want_tags=False):
         serr = np.zeros(max(tot, 1), np.int8)
     args = (h, n, _ptr(payload), _ptr(off), _ptr(sz), int(payload.size), _ptr(terr),
             _ptr(base) if base is not None else None, _ptr(serr) if want_sigs else None)
+    ttag = stag = None
     if want_tags:
         ttag, stag = np.zeros(max(n, 1), np.uint64), np.zeros(max(tot, 1), np.uint64)
+    if want_desc:
+        doff, desc = _desc_buffers(sz)
+        rc = getattr(lib(), name + "_desc")(*args, _ptr(ttag) if want_tags else None, _ptr(stag) if want_tags else None,
+                                            _ptr(doff), _ptr(desc), int(desc.size))
+    elif want_tags:
         rc = getattr(lib(), name + "_tag")(*args, _ptr(ttag), _ptr(stag))
     else:
         rc = getattr(lib(), name)(*args)
@@ -560,6 +602,8 @@ def _verify_txns(name, h, payload, txn_off, txn_sz, want_sigs, want_tags=False):
         out += (base, serr[:int(base[-1])])
     if want_tags:
         out += (ttag[:n], stag[:int(base[-1])])
+    if want_desc:
+        out += (doff, desc[:int(doff[-1])])
     return out if len(out) > 1 else out[0]
 
 
@@ -882,6 +926,22 @@ LATENCY_BATCH_MAX_DEFAULT = 8192
 POOL_BATCH_MIN_DEFAULT = 1 << 19   # k_dsmp from 2^19 signatures
 FD_TXN_AMD_ERR_PARSE = -4
 FD_TXN_MAX_SZ = 3570
+
+
+def txn_parse_packed_scratch_footprint(txn_cnt):
+    """fd_txn_amd_parse_packed_scratch_footprint (no device)."""
+    return int(lib().fd_txn_amd_parse_packed_scratch_footprint(int(txn_cnt)))
+
+
+def txn_parse_packed_dev(txn_cnt, d_payload, d_toff, d_tsz, d_fp, d_desc_off, d_desc, desc_cap, d_scratch, stream=0):
+    """Device batch parse with packed descriptors (fd_txn_amd_parse_packed_dev):
+    footprints, their 64-bit running sum d_desc_off[txn_cnt+1] and the
+    descriptors end to end in d_desc[desc_cap]; device pointers as ints,
+    d_scratch of txn_parse_packed_scratch_footprint(txn_cnt) bytes."""
+    rc = lib().fd_txn_amd_parse_packed_dev(int(txn_cnt), d_payload, d_toff, d_tsz, d_fp, d_desc_off, d_desc, int(desc_cap),
+                                           d_scratch, stream)
+    if rc:
+        raise EngineError("fd_txn_amd_parse_packed_dev rc=%d" % rc)
 
 
 def txn_parse_dev(txn_cnt, d_payload, d_toff, d_tsz, d_fp, d_out=None, out_stride=0, stream=0):

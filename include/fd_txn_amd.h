@@ -287,6 +287,134 @@ fd_ed25519_amd_verify_txns_registered_tag( fd_ed25519_amd_t *   eng,
                                            ulong *              txn_tag,
                                            ulong *              sig_tag );
 
+/* ===== Packed descriptors =====
+
+   The fd_txn_t of every transaction that parses, laid end to end with an
+   offset table, from the GPU parser -- so that what sits behind a verify
+   tile (dedup, pack, the bank) need not run fd_txn_parse again on the CPU.
+
+   Layout, the same in all three calls below:
+     desc_off[0] = 0, desc_off[t+1] = desc_off[t] + footprint[t], txn_cnt+1
+     entries, where footprint[t] is what fd_txn_parse returns for payload t
+     (0 for a payload it rejects).  Footprints are even, so every offset is
+     even; there is no padding between descriptors, and the running sum is
+     carried in 64 bits.
+     The descriptor of an accepted transaction t is the footprint[t] bytes at
+     desc + desc_off[t], byte-identical to what fd_txn_parse writes.  A
+     rejected payload occupies no bytes and no byte is written for it.
+
+   Out of scope: the multi-device forms (a shard's base depends on the other
+   shards' totals), the streaming tile (its 1408-B output frames have no room
+   for a 3570-B descriptor), the drop-in call, and filtering descriptors by
+   verdict. */
+
+/* Upper bound on fd_txn_parse's footprint for ANY payload of payload_sz
+   bytes (pure host code): 0 below 134 bytes, the smallest payload that
+   parses (1 + 64 + 3 + 1 + 32 + 32 + 1), and above FD_TXN_AMD_PAYLOAD_MAX;
+   otherwise 20 + 10*((payload_sz - 134)/3), capped at FD_TXN_MAX_SZ up to
+   FD_TXN_AMD_MTU.  Every instruction takes at least 3 payload bytes for its
+   10 descriptor bytes and every lookup table at least 34 for its 8, so with
+   i instructions and l tables 3 i + 34 l <= payload_sz - 134 and the
+   footprint 20 + 10 i + 8 l <= 20 + 10 (i + 11 l) <= the bound.  It is
+   reached: 355 empty instructions at the MTU have footprint 3570. */
+ulong
+fd_txn_amd_desc_bound( ulong payload_sz );
+
+/* Device-resident packed parse: fd_txn_amd_parse_dev's inputs (payloads up
+   to 65535 B are accepted, as there); d_footprint[txn_cnt] as there;
+   d_desc_off[txn_cnt+1] (8-aligned) and d_desc (2-aligned) in the layout
+   above.  Capacity: descriptor t is stored only if d_desc_off[t+1] <=
+   desc_cap, otherwise nothing of it is; no byte at or beyond d_desc +
+   desc_cap is ever written (d_desc may be NULL when desc_cap is 0);
+   d_desc_off is complete either way, so d_desc_off[txn_cnt] > desc_cap tells
+   the caller that the tail is missing.  d_scratch: at least
+   fd_txn_amd_parse_packed_scratch_footprint( txn_cnt ) bytes of device
+   memory, 8-aligned, contents irrelevant.  Enqueued on `stream` without a
+   sync; txn_cnt == 0 writes d_desc_off[0] only.
+
+   A validate-only parse gives the footprints, an exclusive scan the offsets,
+   and a second walk of the accepted payloads stores each descriptor at its
+   offset (the parser stores records while it walks, before it knows that
+   the payload is acceptable, so the first walk cannot have the final
+   destination).  The scan is kernels ordered by the stream -- per-block
+   totals, one workgroup that loops over them, a per-block pass -- and no
+   workgroup ever waits for another. */
+int
+fd_txn_amd_parse_packed_dev( ulong         txn_cnt,
+                             uchar const * d_payload,
+                             uint const *  d_txn_off,
+                             uint const *  d_txn_sz,
+                             uint *        d_footprint,
+                             ulong *       d_desc_off,
+                             uchar *       d_desc,
+                             ulong         desc_cap,
+                             void *        d_scratch,
+                             void *        stream );
+
+ulong
+fd_txn_amd_parse_packed_scratch_footprint( ulong txn_cnt );
+
+/* fd_ed25519_amd_verify_txns_tag / fd_ed25519_amd_verify_txns_registered_tag
+   that also return the packed descriptors.  desc_off (txn_cnt+1 entries) and
+   desc (desc_cap bytes) are plain caller memory, numbered over the whole
+   batch in the layout above; every other output is exactly that of the _tag
+   call for the same arguments, in the engine's verdict mode.  A descriptor
+   is returned for every transaction that parses, whatever its signatures'
+   verdicts (descriptors do not depend on the mode):
+   desc_off[t+1] == desc_off[t] exactly where txn_err[t] ==
+   FD_TXN_AMD_ERR_PARSE, the registered call's fail-closed rejection of a
+   payload whose parsed signature count differs from its reserved slots
+   included.
+
+   desc_off == NULL (then desc must be NULL too) is exactly the _tag call:
+   nothing more is allocated, launched or copied; the _tag functions are
+   these with NULL.
+
+   Checked with the other arguments, before anything launches and with every
+   output left untouched: desc given without desc_off or desc_off without
+   desc, and desc_cap smaller than the sum of fd_txn_amd_desc_bound(
+   txn_sz[t] ) over the batch, return FD_ED25519_AMD_ERR_INVAL.  Capacity is
+   decided by the bound and never by the data, so a batch that passes cannot
+   overflow.  On an error return the contents of desc and desc_off are
+   unspecified, as for the verdicts and tags.
+
+   Per chunk the descriptors are packed in device memory and one kernel
+   copies the chunk's offsets and bytes to the slot's mapped host staging,
+   reading the byte total on the device; the host adds the running byte base
+   when it drains the slot, chunks in the order they were launched.  The
+   staging (per slot at most min( 3570*batch_max, 20*batch_max +
+   10*blob_max/3 ) bytes, device and pinned host) is allocated by the first
+   call that asks for descriptors. */
+int
+fd_ed25519_amd_verify_txns_desc( fd_ed25519_amd_t * eng,
+                                 ulong              txn_cnt,
+                                 uchar const *      payload,
+                                 uint const *       txn_off,
+                                 uint const *       txn_sz,
+                                 ulong              payload_sz,
+                                 schar *            txn_err,
+                                 uint *             sig_base,
+                                 schar *            sig_err,
+                                 ulong *            txn_tag,
+                                 ulong *            sig_tag,
+                                 ulong *            desc_off,
+                                 uchar *            desc,
+                                 ulong              desc_cap );
+
+int
+fd_ed25519_amd_verify_txns_registered_desc( fd_ed25519_amd_t *   eng,
+                                            ulong                txn_cnt,
+                                            void const * const * txn,
+                                            ulong const *        txn_sz,
+                                            schar *              txn_err,
+                                            uint *               sig_base,
+                                            schar *              sig_err,
+                                            ulong *              txn_tag,
+                                            ulong *              sig_tag,
+                                            ulong *              desc_off,
+                                            uchar *              desc,
+                                            ulong                desc_cap );
+
 /* Signature-slot numbering of a pointer-array batch (pure host code, no
    device): the rule of fd_ed25519_amd_txn_slots, one payload per pointer.
    txn[t] is not looked at when txn_sz[t] is 0, and a NULL txn[t] reserves
