@@ -102,11 +102,35 @@ slot_alloc( slot_t * s, ulong cap, ulong blob_cap ) {
   return FD_ED25519_AMD_OK;
 }
 
+/* The slots' completion words (fd_ed25519_engine.h): mapped and coherent as
+   h_err is, 64 bytes apart so that no two slots' stores share a line, zero
+   to begin with (no ticket is 0). */
+static int
+engine_alloc_ticks( fd_ed25519_amd_t * e ) {
+  HIPCHK( hipHostMalloc( (void **)&e->h_tickbuf, 64UL*(ulong)e->nslot, hipHostMallocMapped | hipHostMallocCoherent ) );
+  memset( e->h_tickbuf, 0, 64UL*(ulong)e->nslot );
+  void * m = NULL;
+  HIPCHK( hipHostGetDevicePointer( &m, e->h_tickbuf, 0 ) );
+  for( int k=0; k<e->nslot; k++ ) {
+    e->slot[k].h_tick = (ulong *)(e->h_tickbuf + 64UL*(ulong)k);
+    e->slot[k].m_tick = (uint8_t *)m + 64UL*(ulong)k;
+  }
+  return FD_ED25519_AMD_OK;
+}
+
 extern "C" fd_ed25519_amd_t *
 fd_ed25519_amd_new( int device, ulong batch_max, ulong blob_max ) {
-  int nslot = 2;
+  ulong nslot = 2UL;
   char const * ev = getenv( "FD_ED25519_AMD_NSLOT" );
-  if( ev && atoi( ev ) >= 2 && atoi( ev ) <= FD_AMD_SLOT_MAX ) nslot = atoi( ev );
+  if( ev && atoi( ev ) >= 2 && atoi( ev ) <= FD_AMD_SLOT_MAX ) nslot = (ulong)atoi( ev );
+  return fd_ed25519_amd_new_slots( device, batch_max, blob_max, nslot );
+}
+
+extern "C" fd_ed25519_amd_t *
+fd_ed25519_amd_new_slots( int device, ulong batch_max, ulong blob_max, ulong slots ) {
+  if( slots < 2UL || slots > (ulong)FD_AMD_SLOT_MAX ) return NULL;   /* before anything touches a device */
+  int const nslot = (int)slots;
+  char const * ev;
   if( !batch_max ) batch_max = 1;
   if( batch_max > (1UL<<26) ) return NULL;
   if( blob_max < FD_ED25519_AMD_MSG_MAX ) blob_max = FD_ED25519_AMD_MSG_MAX;
@@ -130,8 +154,11 @@ fd_ed25519_amd_new( int device, ulong batch_max, ulong blob_max ) {
   int pnode = fd_amd_numa_prefer_begin( device, &pmode, pmask );
   int bad = 0;
   for( int k=0; k<nslot && !bad; k++ ) bad = slot_alloc( &e->slot[k], batch_max, blob_max );
+  if( !bad ) bad = engine_alloc_ticks( e );
   if( pnode >= 0 ) fd_amd_numa_prefer_end( pmode, pmask );
   if( bad ) { fd_ed25519_amd_delete( e ); return NULL; }
+  ev = getenv( "FD_ED25519_AMD_ASYNC_POLL" );
+  e->poll_event = ev && !strcmp( ev, "event" );
   return e;
 }
 
@@ -140,6 +167,7 @@ fd_ed25519_amd_delete( fd_ed25519_amd_t * e ) {
   if( !e ) return;
   (void)hipSetDevice( e->device );
   for( int k=0; k<FD_AMD_SLOT_MAX; k++ ) { if( e->slot[k].stream ) (void)hipStreamSynchronize( e->slot[k].stream ); slot_free( &e->slot[k] ); }
+  if( e->h_tickbuf ) (void)hipHostFree( e->h_tickbuf );
   free( e );
 }
 
@@ -261,7 +289,18 @@ engine_quiesce( fd_ed25519_amd_t * e, int rc ) {
     s->do_out = NULL;
     s->busy = 0;
   }
+  e->a_cnt = 0; e->a_head = e->a_tail;   /* every submission in flight is dropped */
   return rc;
+}
+
+/* The end of every chunk's launch: the slot's event behind all of it.  A
+   submission that polls its completion word has k_ticket store its ticket
+   there first, the last kernel on the stream. */
+static int
+slot_done( slot_t * s ) {
+  if( s->tick_arm && fd_amd_launch_ticket( s->m_tick, s->ticket, s->stream ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  HIPCHK( hipEventRecord( s->done, s->stream ) );
+  return FD_ED25519_AMD_OK;
 }
 
 /* The chunk just launched on s is in flight: n verdicts, written to h_err,
@@ -296,7 +335,7 @@ slot_launch_packed( slot_t * s, ulong n, ulong blob_sz, schar * out, ulong * tag
      the DSM kernel costs the same one launch; after it, the verify launch
      sequence is the untagged call's */
   if( tag && slot_tags( s, n ) ) return FD_ED25519_AMD_ERR_DEVICE;
-  HIPCHK( hipEventRecord( s->done, s->stream ) );
+  if( slot_done( s ) ) return FD_ED25519_AMD_ERR_DEVICE;
   slot_in_flight( s, out, tag, n );
   return FD_ED25519_AMD_OK;
 }
@@ -352,7 +391,7 @@ slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, schar * t_out, schar * s_
         fd_amd_launch_desc_out( s->m_desc, s->d_desc, s->m_doff, s->d_doff, (uint32_t)c, s->desc_stage, dq->bound, s->stream ) )
       return FD_ED25519_AMD_ERR_DEVICE;
   }
-  HIPCHK( hipEventRecord( s->done, s->stream ) );
+  if( slot_done( s ) ) return FD_ED25519_AMD_ERR_DEVICE;
   s->do_out = dq ? dq->off : NULL; s->do_n = c;
   if( dq ) { s->d_out = dq->desc; s->d_cap = dq->cap; s->d_base = dq->base; }
   s->tg_out = tt_out; s->tg_n = c;
@@ -389,6 +428,52 @@ run_ring( fd_ed25519_amd_t * e, int ring, ulong total, STAGE stage ) {
   return FD_ED25519_AMD_OK;
 }
 
+/* Submissions in flight hold slots the synchronous calls (and a mode change)
+   would reuse: those refuse, before they touch anything. */
+#define SYNC_REFUSED( e ) ( (e) && (e)->a_cnt )
+
+/* The argument check of the staged pointer-array calls. */
+static int
+batch_args_check( fd_ed25519_amd_t const * e, ulong n, void const * const * msg, ulong const * sz,
+                  void const * const * sig, void const * const * pub, schar const * err ) {
+  if( !e || (n && (!msg || !sz || !sig || !pub || !err)) ) return FD_ED25519_AMD_ERR_INVAL;
+  for( ulong j=0; j<n; j++ )            /* every message must fit one chunk: checked before anything launches */
+    if( sz[j] > e->blob_cap || (sz[j] && !msg[j]) ) return FD_ED25519_AMD_ERR_INVAL;
+  return FD_ED25519_AMD_OK;
+}
+
+/* The chunk the staged pointer-array call cuts off the front of n signatures. */
+static ulong
+batch_chunk( fd_ed25519_amd_t const * e, ulong n, ulong const * sz ) {
+  ulong c = 0, bsz = 0;
+  while( c < n && c < e->cap && bsz + sz[c] <= e->blob_cap ) { bsz += sz[c]; c++; }
+  return c;
+}
+
+/* Stage and launch on s the first chunk of the n signatures given (the
+   arrays start at the chunk's first signature); returns the signatures
+   taken or an error code. */
+static long
+stage_batch( fd_ed25519_amd_t * e, slot_t * s, ulong n, void const * const * msg, ulong const * sz,
+             void const * const * sig, void const * const * pub, schar * err, ulong * tag ) {
+  if( tag ) { int rc = slot_alloc_tag( s, e->cap ); if( rc ) return rc; }
+  /* size the chunk first, then stage it packed: [pub|sig|off|sz|blob] */
+  ulong const c = batch_chunk( e, n, sz );
+  uint8_t * hp = s->h_pack;
+  uint8_t * h_pub = hp, * h_sig = hp + 32UL*c, * h_blob = hp + 104UL*c;
+  uint32_t * h_off = (uint32_t *)(hp + 96UL*c), * h_sz = (uint32_t *)(hp + 100UL*c);
+  ulong bsz = 0;
+  for( ulong j=0; j<c; j++ ) {
+    memcpy( h_pub + 32UL*j, pub[j], 32 );
+    memcpy( h_sig + 64UL*j, sig[j], 64 );
+    if( sz[j] ) memcpy( h_blob + bsz, msg[j], sz[j] );
+    h_off[j] = (uint32_t)bsz; h_sz[j] = (uint32_t)sz[j];
+    bsz += sz[j];
+  }
+  int rc = slot_launch_packed( s, c, bsz, err, tag );
+  return rc ? rc : (long)c;
+}
+
 extern "C" int
 fd_ed25519_amd_verify_batch( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
                              void const * const * sig, void const * const * pub, schar * err ) {
@@ -398,27 +483,11 @@ fd_ed25519_amd_verify_batch( fd_ed25519_amd_t * e, ulong n, void const * const *
 extern "C" int
 fd_ed25519_amd_verify_batch_tag( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
                                  void const * const * sig, void const * const * pub, schar * err, ulong * tag ) {
-  if( !e || (n && (!msg || !sz || !sig || !pub || !err)) ) return FD_ED25519_AMD_ERR_INVAL;
-  for( ulong j=0; j<n; j++ )            /* every message must fit one chunk: checked before anything launches */
-    if( sz[j] > e->blob_cap || (sz[j] && !msg[j]) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( SYNC_REFUSED( e ) ) return FD_ED25519_AMD_ERR_INVAL;
+  int rc = batch_args_check( e, n, msg, sz, sig, pub, err );
+  if( rc ) return rc;
   return run_ring( e, 2, n, [&]( slot_t * s, ulong i ) -> long {
-    if( tag ) { int rc = slot_alloc_tag( s, e->cap ); if( rc ) return rc; }
-    /* size the chunk first, then stage it packed: [pub|sig|off|sz|blob] */
-    ulong c = 0, bsz = 0;
-    while( i + c < n && c < e->cap && bsz + sz[i+c] <= e->blob_cap ) { bsz += sz[i+c]; c++; }
-    uint8_t * hp = s->h_pack;
-    uint8_t * h_pub = hp, * h_sig = hp + 32UL*c, * h_blob = hp + 104UL*c;
-    uint32_t * h_off = (uint32_t *)(hp + 96UL*c), * h_sz = (uint32_t *)(hp + 100UL*c);
-    bsz = 0;
-    for( ulong j=0; j<c; j++ ) {
-      memcpy( h_pub + 32UL*j, pub[i+j], 32 );
-      memcpy( h_sig + 64UL*j, sig[i+j], 64 );
-      if( sz[i+j] ) memcpy( h_blob + bsz, msg[i+j], sz[i+j] );
-      h_off[j] = (uint32_t)bsz; h_sz[j] = (uint32_t)sz[i+j];
-      bsz += sz[i+j];
-    }
-    int rc = slot_launch_packed( s, c, bsz, err + i, tag ? tag + i : NULL );
-    return rc ? rc : (long)c;
+    return stage_batch( e, s, n - i, msg + i, sz + i, sig + i, pub + i, err + i, tag ? tag + i : NULL );
   } );
 }
 
@@ -516,6 +585,7 @@ extern "C" int
 fd_ed25519_amd_verify_soa_tag( fd_ed25519_amd_t * e, ulong n, uchar const * pub, uchar const * sig,
                                uint const * msg_off, uint const * msg_sz, uchar const * blob, ulong blob_sz,
                                schar * err, ulong * tag ) {
+  if( SYNC_REFUSED( e ) ) return FD_ED25519_AMD_ERR_INVAL;
   int rc = fd_amd_soa_args_check( e, n, pub, sig, msg_off, msg_sz, blob, blob_sz, err );
   if( rc ) return rc;
   return run_ring( e, e->nslot, n, [&]( slot_t * s, ulong i ) -> long {
@@ -612,7 +682,7 @@ slot_launch_dma( slot_t * s, ulong c, uchar const * pub, uchar const * sig, uint
     return FD_ED25519_AMD_ERR_DEVICE;
   HIPCHK( slot_out( s, s->m_err, s->d_err, c ) );
   if( tag && slot_tags( s, c ) ) return FD_ED25519_AMD_ERR_DEVICE;
-  HIPCHK( hipEventRecord( s->done, s->stream ) );
+  if( slot_done( s ) ) return FD_ED25519_AMD_ERR_DEVICE;
   slot_in_flight( s, out, tag, c );
   return FD_ED25519_AMD_OK;
 }
@@ -628,6 +698,7 @@ extern "C" int
 fd_ed25519_amd_verify_soa_registered_tag( fd_ed25519_amd_t * e, ulong n, uchar const * pub, uchar const * sig,
                                           uint const * msg_off, uint const * msg_sz, uchar const * blob, ulong blob_sz,
                                           schar * err, ulong * tag ) {
+  if( SYNC_REFUSED( e ) ) return FD_ED25519_AMD_ERR_INVAL;
   int rc = fd_amd_soa_args_check( e, n, pub, sig, msg_off, msg_sz, blob, blob_sz, err );
   if( rc ) return rc;
   if( !n ) return FD_ED25519_AMD_OK;
@@ -745,9 +816,63 @@ slot_launch_gather( slot_t * s, ulong c, bool copy, schar * out, ulong * tag ) {
     return FD_ED25519_AMD_ERR_DEVICE;
   if( !lat ) HIPCHK( slot_out( s, s->m_err, s->d_err, c ) );
   if( tag && slot_tags( s, c ) ) return FD_ED25519_AMD_ERR_DEVICE;
-  HIPCHK( hipEventRecord( s->done, s->stream ) );
+  if( slot_done( s ) ) return FD_ED25519_AMD_ERR_DEVICE;
   slot_in_flight( s, out, tag, c );
   return FD_ED25519_AMD_OK;
+}
+
+/* Every signature of a registered pointer-array batch, before anything
+   launches: its pointers, its size, and the first and last byte of each
+   range in one registration of the table.  True when all pass. */
+static bool
+batch_registered_check( fd_ed25519_amd_t const * e, reg_view_t const & view, ulong n, void const * const * msg,
+                        ulong const * sz, void const * const * sig, void const * const * pub ) {
+  auto check = [&]( ulong lo, ulong hi ) -> bool {
+    reg_view_t v = view;                     /* its own last-hit index */
+    fd_amd_gather_rec_t probe;
+    for( ulong j=lo; j<hi; j++ )
+      if( sz[j] > e->blob_cap || !v.rec( &probe, pub[j], sig[j], msg[j], sz[j] ) ) return false;
+    return true;
+  };
+  /* the pass reads 32 B of pointers and sizes per signature and nothing of
+     it overlaps the GPU: large batches split it over up to 4 host threads,
+     as copy_par does the staging copies */
+  int nt = (int)( n >> 17 ); if( nt > 4 ) nt = 4;
+  if( nt < 2 ) return check( 0UL, n );
+  std::thread th[3]; bool ok[4];
+  ulong const part = ( n + (ulong)nt - 1UL ) / (ulong)nt;
+  for( int t=1; t<nt; t++ ) th[t-1] = std::thread( [&, t]{ ok[t] = check( part*(ulong)t, std::min( n, part*(ulong)(t+1) ) ); } );
+  ok[0] = check( 0UL, part );
+  for( int t=1; t<nt; t++ ) th[t-1].join();
+  for( int t=0; t<nt; t++ ) if( !ok[t] ) return false;
+  return true;
+}
+
+/* Where a slot keeps a gathered chunk's dst offsets: behind its records in
+   h_pack. */
+static inline uint *
+slot_gather_dst( fd_ed25519_amd_t const * e, slot_t * s ) { return (uint *)(s->h_pack + 32UL*e->cap); }
+
+/* Stage and launch on s the first chunk of the n registered signatures given
+   (the arrays start at the chunk's first signature); returns the signatures
+   taken or an error code. */
+static long
+stage_batch_registered( fd_ed25519_amd_t * e, slot_t * s, reg_view_t & view, ulong n, void const * const * msg,
+                        ulong const * sz, void const * const * sig, void const * const * pub, schar * err, ulong * tag ) {
+  if( tag ) { int rc = slot_alloc_tag( s, e->cap ); if( rc ) return rc; }
+  /* the chunk's records in h_pack (32 B per signature), their dst behind them */
+  fd_amd_gather_rec_t * rec = (fd_amd_gather_rec_t *)s->h_pack;
+  uint * dst = slot_gather_dst( e, s );
+  ulong c = fd_ed25519_amd_gather_layout( n, sz, e->cap, e->blob_cap, dst );
+  for( ulong j=0; j<c; j++ ) {
+    /* translated again, not kept from the check: the chunk's translation
+       runs beside the previous chunk's kernels, a table of n records would
+       not; an address the table does not give never reaches the kernel */
+    if( sz[j] > e->blob_cap || !view.rec( rec + j, pub[j], sig[j], msg[j], sz[j] ) ) return FD_ED25519_AMD_ERR_INVAL;
+    rec[j].dst = dst[j];
+  }
+  int rc = slot_launch_gather( s, c, e->gather_copy != 0, err, tag );
+  return rc ? rc : (long)c;
 }
 
 extern "C" int
@@ -760,46 +885,13 @@ extern "C" int
 fd_ed25519_amd_verify_batch_registered_tag( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
                                             void const * const * sig, void const * const * pub, schar * err,
                                             ulong * tag ) {
+  if( SYNC_REFUSED( e ) ) return FD_ED25519_AMD_ERR_INVAL;
   if( !e || (n && (!msg || !sz || !sig || !pub || !err)) ) return FD_ED25519_AMD_ERR_INVAL;
   if( !n ) return FD_ED25519_AMD_OK;
   reg_view_t view;
-  /* every signature before anything launches: its pointers, its size, and
-     the first and last byte of each range in one registration of the table */
-  auto check = [&]( ulong lo, ulong hi ) -> bool {
-    reg_view_t v = view;                     /* its own last-hit index */
-    fd_amd_gather_rec_t probe;
-    for( ulong j=lo; j<hi; j++ )
-      if( sz[j] > e->blob_cap || !v.rec( &probe, pub[j], sig[j], msg[j], sz[j] ) ) return false;
-    return true;
-  };
-  /* the pass reads 32 B of pointers and sizes per signature and nothing of
-     it overlaps the GPU: large batches split it over up to 4 host threads,
-     as copy_par does the staging copies */
-  int nt = (int)( n >> 17 ); if( nt > 4 ) nt = 4;
-  if( nt < 2 ) { if( !check( 0UL, n ) ) return FD_ED25519_AMD_ERR_INVAL; }
-  else {
-    std::thread th[3]; bool ok[4];
-    ulong const part = ( n + (ulong)nt - 1UL ) / (ulong)nt;
-    for( int t=1; t<nt; t++ ) th[t-1] = std::thread( [&, t]{ ok[t] = check( part*(ulong)t, std::min( n, part*(ulong)(t+1) ) ); } );
-    ok[0] = check( 0UL, part );
-    for( int t=1; t<nt; t++ ) th[t-1].join();
-    for( int t=0; t<nt; t++ ) if( !ok[t] ) return FD_ED25519_AMD_ERR_INVAL;
-  }
+  if( !batch_registered_check( e, view, n, msg, sz, sig, pub ) ) return FD_ED25519_AMD_ERR_INVAL;
   return run_ring( e, e->nslot, n, [&]( slot_t * s, ulong i ) -> long {
-    if( tag ) { int rc = slot_alloc_tag( s, e->cap ); if( rc ) return rc; }
-    /* the chunk's records in h_pack (32 B per signature), their dst behind them */
-    fd_amd_gather_rec_t * rec = (fd_amd_gather_rec_t *)s->h_pack;
-    uint * dst = (uint *)(s->h_pack + 32UL*e->cap);
-    ulong c = fd_ed25519_amd_gather_layout( n - i, sz + i, e->cap, e->blob_cap, dst );
-    for( ulong j=0; j<c; j++ ) {
-      /* translated again, not kept from the check: the chunk's translation
-         runs beside the previous chunk's kernels, a table of n records would
-         not; an address the table does not give never reaches the kernel */
-      if( sz[i+j] > e->blob_cap || !view.rec( rec + j, pub[i+j], sig[i+j], msg[i+j], sz[i+j] ) ) return FD_ED25519_AMD_ERR_INVAL;
-      rec[j].dst = dst[j];
-    }
-    int rc = slot_launch_gather( s, c, e->gather_copy != 0, err + i, tag ? tag + i : NULL );
-    return rc ? rc : (long)c;
+    return stage_batch_registered( e, s, view, n - i, msg + i, sz + i, sig + i, pub + i, err + i, tag ? tag + i : NULL );
   } );
 }
 
@@ -858,44 +950,101 @@ fd_txn_amd_desc_bound( ulong payload_sz ) {
   return ( payload_sz <= FD_TXN_AMD_MTU && b > FD_TXN_MAX_SZ ) ? FD_TXN_MAX_SZ : b;
 }
 
+/* Where one transaction chunk's outputs go: the caller's arrays at the
+   chunk's first transaction (txn_err, txn_tag, desc_off) and first signature
+   slot (sig_err, sig_tag), NULL where not asked for; the whole descriptor
+   buffer, and the call's running descriptor byte base. */
+struct txn_outs_t {
+  schar * txn_err; schar * sig_err; ulong * txn_tag; ulong * sig_tag;
+  ulong * desc_off; uchar * desc; ulong desc_cap; ulong * dbase;
+};
+
+/* The first buffers a transaction chunk needs on its slot. */
+static int
+slot_alloc_txn( fd_ed25519_amd_t const * e, slot_t * s, txn_outs_t const & o ) {
+  int rc = slot_alloc_aux( s, e->cap );
+  if( !rc && (o.txn_tag || o.sig_tag) ) rc = slot_alloc_tag( s, e->cap );
+  if( !rc && o.desc_off ) rc = slot_alloc_desc( s, e->cap, e->blob_cap );
+  return rc;
+}
+
+/* The argument check of the staged transaction calls (the descriptor
+   capacity is decided by the bound, never by the data). */
+static int
+txns_args_check( fd_ed25519_amd_t const * e, ulong txn_cnt, uchar const * payload, uint const * txn_off, uint const * txn_sz,
+                 ulong payload_sz, schar const * txn_err, uint const * sig_base, schar const * sig_err, ulong const * sig_tag,
+                 ulong const * desc_off, uchar const * desc, ulong desc_cap ) {
+  int rc = fd_amd_txn_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag );
+  if( rc ) return rc;
+  if( !desc != !desc_off ) return FD_ED25519_AMD_ERR_INVAL;
+  if( desc_off ) {
+    ulong need = 0;
+    for( ulong t=0; t<txn_cnt; t++ ) need += fd_txn_amd_desc_bound( txn_sz[t] );
+    if( desc_cap < need ) return FD_ED25519_AMD_ERR_INVAL;
+  }
+  return FD_ED25519_AMD_OK;
+}
+
+/* The chunk the staged transaction call cuts off the front of txn_cnt
+   transactions: bounded by their count, their signature slots and their
+   bytes. */
+static ulong
+txns_chunk( fd_ed25519_amd_t const * e, ulong txn_cnt, uchar const * payload, uint const * txn_off, uint const * txn_sz ) {
+  ulong c = 0, bsz = 0, ns = 0;
+  while( c < txn_cnt && c < e->cap ) {
+    ulong sz = txn_sz[c], k2 = fd_amd_txn_slots1( payload + txn_off[c], sz );
+    if( bsz + sz > e->blob_cap || ns + k2 > e->cap ) break;
+    bsz += sz; ns += k2; c++;
+  }
+  return c;
+}
+
+/* Stage and launch on s the first chunk of the txn_cnt transactions given
+   (txn_off and txn_sz start at the chunk's first transaction); returns the
+   transactions taken or an error code, and in *slots the signature slots
+   they reserve. */
+static long
+stage_txns( fd_ed25519_amd_t * e, slot_t * s, ulong txn_cnt, uchar const * payload, uint const * txn_off,
+            uint const * txn_sz, txn_outs_t const & o, ulong * slots ) {
+  int rc = slot_alloc_txn( e, s, o );
+  if( rc ) return rc;
+  ulong c = 0, bsz = 0, ns = 0;
+  desc_req_t dq = { o.desc_off, o.desc, o.desc_cap, o.dbase, 0UL };
+  while( c < txn_cnt && c < e->cap ) {
+    uchar const * p = payload + txn_off[c];
+    ulong sz = txn_sz[c], k2 = fd_amd_txn_slots1( p, sz );
+    if( bsz + sz > e->blob_cap || ns + k2 > e->cap ) break;   /* txns_chunk's rule */
+    if( sz ) memcpy( s->h_blob + bsz, p, sz );
+    s->h_toff[c] = (uint32_t)bsz; s->h_tsz[c] = (uint32_t)sz; s->h_tbase[c] = (uint32_t)ns;
+    if( o.desc_off ) dq.bound += fd_txn_amd_desc_bound( sz );
+    bsz += sz; ns += k2; c++;
+  }
+  s->h_tbase[c] = (uint32_t)ns;
+  rc = slot_launch_txn( s, c, ns, bsz, o.txn_err, o.sig_err, o.txn_tag, o.sig_tag, o.desc_off ? &dq : NULL );
+  *slots = ns;
+  return rc ? rc : (long)c;
+}
+
 extern "C" int
 fd_ed25519_amd_verify_txns_desc( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
                                  uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                                  ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap ) {
-  int rc = fd_amd_txn_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag );
+  if( SYNC_REFUSED( e ) ) return FD_ED25519_AMD_ERR_INVAL;
+  int rc = txns_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag,
+                            desc_off, desc, desc_cap );
   if( rc ) return rc;
-  if( !desc != !desc_off ) return FD_ED25519_AMD_ERR_INVAL;
-  if( desc_off ) {   /* capacity is decided by the bound, never by the data */
-    ulong need = 0;
-    for( ulong t=0; t<txn_cnt; t++ ) need += fd_txn_amd_desc_bound( txn_sz[t] );
-    if( desc_cap < need ) return FD_ED25519_AMD_ERR_INVAL;
-    desc_off[0] = 0UL;
-  }
+  if( desc_off ) desc_off[0] = 0UL;
   ulong dbase = 0;   /* descriptor bytes of the chunks delivered so far */
   /* global signature numbering (the caller-visible sig_base) */
   if( sig_base ) fd_ed25519_amd_txn_slots( txn_cnt, payload, txn_off, txn_sz, sig_base );
   ulong gsig = 0;
   return run_ring( e, 2, txn_cnt, [&]( slot_t * s, ulong t ) -> long {
-    int rc = slot_alloc_aux( s, e->cap );
-    if( !rc && (txn_tag || sig_tag) ) rc = slot_alloc_tag( s, e->cap );
-    if( !rc && desc_off ) rc = slot_alloc_desc( s, e->cap, e->blob_cap );
-    if( rc ) return rc;
-    ulong c = 0, bsz = 0, ns = 0;
-    desc_req_t dq = { desc_off ? desc_off + t : NULL, desc, desc_cap, &dbase, 0UL };
-    while( t + c < txn_cnt && c < e->cap ) {
-      uchar const * p = payload + txn_off[t+c];
-      ulong sz = txn_sz[t+c], k2 = fd_amd_txn_slots1( p, sz );
-      if( bsz + sz > e->blob_cap || ns + k2 > e->cap ) break;
-      if( sz ) memcpy( s->h_blob + bsz, p, sz );
-      s->h_toff[c] = (uint32_t)bsz; s->h_tsz[c] = (uint32_t)sz; s->h_tbase[c] = (uint32_t)ns;
-      if( desc_off ) dq.bound += fd_txn_amd_desc_bound( sz );
-      bsz += sz; ns += k2; c++;
-    }
-    s->h_tbase[c] = (uint32_t)ns;
-    rc = slot_launch_txn( s, c, ns, bsz, txn_err + t, sig_err ? sig_err + gsig : NULL, txn_tag ? txn_tag + t : NULL,
-                          sig_tag ? sig_tag + gsig : NULL, desc_off ? &dq : NULL );
+    txn_outs_t o = { txn_err + t, sig_err ? sig_err + gsig : NULL, txn_tag ? txn_tag + t : NULL,
+                     sig_tag ? sig_tag + gsig : NULL, desc_off ? desc_off + t : NULL, desc, desc_cap, &dbase };
+    ulong ns = 0;
+    long c = stage_txns( e, s, txn_cnt - t, payload, txn_off + t, txn_sz + t, o, &ns );
     gsig += ns;
-    return rc ? rc : (long)c;
+    return c;
   } );
 }
 
@@ -968,27 +1117,24 @@ fd_ed25519_amd_verify_txns_registered_tag( fd_ed25519_amd_t * e, ulong txn_cnt, 
                                                      NULL, NULL, 0UL );
 }
 
-extern "C" int
-fd_ed25519_amd_verify_txns_registered_desc( fd_ed25519_amd_t * e, ulong txn_cnt, void const * const * txn,
-                                            ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
-                                            ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc,
-                                            ulong desc_cap ) {
-  if( !e || (txn_cnt && (!txn || !txn_sz || !txn_err)) ) return FD_ED25519_AMD_ERR_INVAL;
+/* The argument check of the registered transaction calls, for
+   txn_cnt > 0.  Every transaction before anything launches: its pointer, its
+   size, its first and last byte in one registration of the table, and the
+   signature slots it reserves -- read here, once, from payload[0] into
+   slots[0 .. txn_cnt): the chunks and sig_base use this count, whatever the
+   byte holds later. */
+static int
+txns_registered_check( fd_ed25519_amd_t const * e, reg_view_t const & view, ulong txn_cnt, void const * const * txn,
+                       ulong const * txn_sz, schar const * txn_err, uint const * sig_base, schar const * sig_err,
+                       ulong const * sig_tag, ulong const * desc_off, uchar const * desc, ulong desc_cap, uint * slots ) {
+  if( !txn || !txn_sz || !txn_err ) return FD_ED25519_AMD_ERR_INVAL;
   if( (sig_err || sig_tag) && !sig_base ) return FD_ED25519_AMD_ERR_INVAL;
   if( !desc != !desc_off ) return FD_ED25519_AMD_ERR_INVAL;
-  if( txn_cnt > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
-  if( !txn_cnt ) { if( sig_base ) sig_base[0] = 0U; if( desc_off ) desc_off[0] = 0UL; return FD_ED25519_AMD_OK; }
   if( desc_off ) {   /* capacity is decided by the bound, never by the data */
     ulong need = 0;
     for( ulong t=0; t<txn_cnt; t++ ) need += fd_txn_amd_desc_bound( txn_sz[t] );
     if( desc_cap < need ) return FD_ED25519_AMD_ERR_INVAL;
   }
-  reg_view_t view;
-  /* every transaction before anything launches: its pointer, its size, its
-     first and last byte in one registration of the table, and the signature
-     slots it reserves -- read here, once, from payload[0]: the chunks and
-     sig_base use this count, whatever the byte holds later */
-  std::vector<uint> slots( txn_cnt );
   auto check = [&]( ulong lo, ulong hi ) -> bool {
     reg_view_t v = view;                     /* its own last-hit index */
     for( ulong t=lo; t<hi; t++ ) {
@@ -1015,42 +1161,77 @@ fd_ed25519_amd_verify_txns_registered_desc( fd_ed25519_amd_t * e, ulong txn_cnt,
     for( int t=1; t<nt; t++ ) th[t-1].join();
     for( int t=0; t<nt; t++ ) if( !ok[t] ) return FD_ED25519_AMD_ERR_INVAL;
   }
-  if( desc_off ) desc_off[0] = 0UL;
-  /* global signature numbering (the caller-visible sig_base) */
-  if( sig_base ) {
-    ulong acc = 0;
-    for( ulong t=0; t<txn_cnt; t++ ) { sig_base[t] = (uint)acc; acc += slots[t]; }
-    sig_base[txn_cnt] = (uint)acc;
+  return FD_ED25519_AMD_OK;
+}
+
+/* The caller-visible global signature numbering from the checked counts. */
+static void
+txns_sig_base( ulong txn_cnt, uint const * slots, uint * sig_base ) {
+  ulong acc = 0;
+  for( ulong t=0; t<txn_cnt; t++ ) { sig_base[t] = (uint)acc; acc += slots[t]; }
+  sig_base[txn_cnt] = (uint)acc;
+}
+
+/* Stage and launch on s the first chunk of the txn_cnt registered
+   transactions given (txn, txn_sz and slots start at the chunk's first
+   transaction); returns the transactions taken or an error code, and in
+   *slot_cnt the signature slots they reserve. */
+static long
+stage_txns_registered( fd_ed25519_amd_t * e, slot_t * s, reg_view_t & view, ulong txn_cnt, void const * const * txn,
+                       ulong const * txn_sz, uint const * slots, txn_outs_t const & o, ulong * slot_cnt ) {
+  int rc = slot_alloc_txn( e, s, o );
+  if( rc ) return rc;
+  desc_req_t dq = { o.desc_off, o.desc, o.desc_cap, o.dbase, 0UL };
+  /* the chunk's records in h_pack (32 B per transaction), their dst behind them */
+  fd_amd_gather_txn_rec_t * rec = (fd_amd_gather_txn_rec_t *)s->h_pack;
+  uint * dst = slot_gather_dst( e, s );
+  ulong ns = 0;
+  ulong c = fd_ed25519_amd_txn_gather_layout( txn_cnt, txn_sz, slots, e->cap, e->blob_cap, dst, &ns );
+  ulong b = 0;
+  for( ulong j=0; j<c; j++ ) {
+    /* translated again, not kept from the check (fd_ed25519_amd_verify_batch_registered):
+       an address the table does not give never reaches the kernel */
+    ulong const sz = txn_sz[j];
+    rec[j].src = 0UL;
+    if( sz > FD_TXN_AMD_MTU || sz > e->blob_cap || ( sz && ( !txn[j] || !view.xlat( txn[j], sz, &rec[j].src ) ) ) )
+      return FD_ED25519_AMD_ERR_INVAL;
+    rec[j].sz = (uint32_t)sz; rec[j].dst = dst[j]; rec[j].tbase = (uint32_t)b;
+    if( o.desc_off ) dq.bound += fd_txn_amd_desc_bound( sz );
+    b += slots[j];
   }
+  rc = slot_launch_txn_gather( s, c, ns, (uint)e->gather_txn_waves, o.txn_err, o.sig_err, o.txn_tag, o.sig_tag,
+                               o.desc_off ? &dq : NULL );
+  *slot_cnt = ns;
+  return rc ? rc : (long)c;
+}
+
+extern "C" int
+fd_ed25519_amd_verify_txns_registered_desc( fd_ed25519_amd_t * e, ulong txn_cnt, void const * const * txn,
+                                            ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                                            ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc,
+                                            ulong desc_cap ) {
+  if( SYNC_REFUSED( e ) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !e || (txn_cnt && (!txn || !txn_sz || !txn_err)) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( (sig_err || sig_tag) && !sig_base ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !desc != !desc_off ) return FD_ED25519_AMD_ERR_INVAL;
+  if( txn_cnt > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !txn_cnt ) { if( sig_base ) sig_base[0] = 0U; if( desc_off ) desc_off[0] = 0UL; return FD_ED25519_AMD_OK; }
+  reg_view_t view;
+  std::vector<uint> slots( txn_cnt );
+  int rc = txns_registered_check( e, view, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, sig_tag, desc_off, desc,
+                                  desc_cap, slots.data() );
+  if( rc ) return rc;
+  if( desc_off ) desc_off[0] = 0UL;
+  if( sig_base ) txns_sig_base( txn_cnt, slots.data(), sig_base );
   ulong gsig = 0;
   ulong dbase = 0;   /* descriptor bytes of the chunks delivered so far */
   return run_ring( e, e->nslot, txn_cnt, [&]( slot_t * s, ulong t ) -> long {
-    int rc = slot_alloc_aux( s, e->cap );
-    if( !rc && (txn_tag || sig_tag) ) rc = slot_alloc_tag( s, e->cap );
-    if( !rc && desc_off ) rc = slot_alloc_desc( s, e->cap, e->blob_cap );
-    if( rc ) return rc;
-    desc_req_t dq = { desc_off ? desc_off + t : NULL, desc, desc_cap, &dbase, 0UL };
-    /* the chunk's records in h_pack (32 B per transaction), their dst behind them */
-    fd_amd_gather_txn_rec_t * rec = (fd_amd_gather_txn_rec_t *)s->h_pack;
-    uint * dst = (uint *)(s->h_pack + 32UL*e->cap);
+    txn_outs_t o = { txn_err + t, sig_err ? sig_err + gsig : NULL, txn_tag ? txn_tag + t : NULL,
+                     sig_tag ? sig_tag + gsig : NULL, desc_off ? desc_off + t : NULL, desc, desc_cap, &dbase };
     ulong ns = 0;
-    ulong c = fd_ed25519_amd_txn_gather_layout( txn_cnt - t, txn_sz + t, slots.data() + t, e->cap, e->blob_cap, dst, &ns );
-    ulong b = 0;
-    for( ulong j=0; j<c; j++ ) {
-      /* translated again, not kept from the check (fd_ed25519_amd_verify_batch_registered):
-         an address the table does not give never reaches the kernel */
-      ulong const sz = txn_sz[t+j];
-      rec[j].src = 0UL;
-      if( sz > FD_TXN_AMD_MTU || sz > e->blob_cap || ( sz && ( !txn[t+j] || !view.xlat( txn[t+j], sz, &rec[j].src ) ) ) )
-        return FD_ED25519_AMD_ERR_INVAL;
-      rec[j].sz = (uint32_t)sz; rec[j].dst = dst[j]; rec[j].tbase = (uint32_t)b;
-      if( desc_off ) dq.bound += fd_txn_amd_desc_bound( sz );
-      b += slots[t+j];
-    }
-    rc = slot_launch_txn_gather( s, c, ns, (uint)e->gather_txn_waves, txn_err + t, sig_err ? sig_err + gsig : NULL,
-                                 txn_tag ? txn_tag + t : NULL, sig_tag ? sig_tag + gsig : NULL, desc_off ? &dq : NULL );
+    long c = stage_txns_registered( e, s, view, txn_cnt - t, txn + t, txn_sz + t, slots.data() + t, o, &ns );
     gsig += ns;
-    return rc ? rc : (long)c;
+    return c;
   } );
 }
 
@@ -1222,11 +1403,160 @@ fd_ed25519_amd_verify_dev_ev( ulong n, uchar const * d_pub, uchar const * d_sig,
                                             FD_ED25519_AMD_MODE_REFERENCE );
 }
 
-/* The engine's mode: every later call of this engine launches with it.
-   Calls are synchronous (each drains its chunks), so none is in flight. */
+/* ------------------------------------------------------------------ */
+/* asynchronous submissions: one chunk on one slot, collected later     */
+
+extern "C" ulong
+fd_ed25519_amd_async_depth( fd_ed25519_amd_t const * e ) { return e ? (ulong)e->nslot : 0UL; }
+
+extern "C" ulong
+fd_ed25519_amd_async_in_flight( fd_ed25519_amd_t const * e ) { return e ? (ulong)e->a_cnt : 0UL; }
+
+/* The slot the next submission takes, after the submit call's argument
+   checks: NULL with *rc set when every slot carries one, or the device
+   cannot be made current. */
+static slot_t *
+submit_slot( fd_ed25519_amd_t * e, int * rc ) {
+  if( e->a_cnt >= e->nslot ) { *rc = FD_ED25519_AMD_ERR_BUSY; return NULL; }
+  if( hipSetDevice( e->device ) != hipSuccess ) { *rc = FD_ED25519_AMD_ERR_DEVICE; return NULL; }
+  return &e->slot[e->a_tail];
+}
+
+/* Run a stage function once on s as the next submission.  The ticket is
+   handed out only when the chunk is in flight.  ERR_INVAL from the stage comes
+   before its first launch; any other error quiesces the engine, as in
+   run_ring. */
+template<typename STAGE>
+static int
+submit_run( fd_ed25519_amd_t * e, slot_t * s, ulong * ticket, STAGE stage ) {
+  s->ticket = e->ticket + 1UL;
+  s->tick_arm = !e->poll_event;
+  long c = stage();
+  s->tick_arm = 0;
+  if( c < 0L ) return c == (long)FD_ED25519_AMD_ERR_INVAL ? FD_ED25519_AMD_ERR_INVAL : engine_quiesce( e, (int)c );
+  e->ticket = s->ticket;
+  e->a_tail = (e->a_tail + 1) % e->nslot; e->a_cnt++;
+  *ticket = s->ticket;
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" int
+fd_ed25519_amd_submit_batch( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
+                             void const * const * sig, void const * const * pub, schar * err, ulong * tag, ulong * ticket ) {
+  if( !e || !ticket || !n ) return FD_ED25519_AMD_ERR_INVAL;
+  int rc = batch_args_check( e, n, msg, sz, sig, pub, err );
+  if( rc ) return rc;
+  slot_t * s = submit_slot( e, &rc );
+  if( !s ) return rc;
+  if( batch_chunk( e, n, sz ) != n ) return FD_ED25519_AMD_ERR_INVAL;   /* one chunk */
+  return submit_run( e, s, ticket, [&]() -> long { return stage_batch( e, s, n, msg, sz, sig, pub, err, tag ); } );
+}
+
+extern "C" int
+fd_ed25519_amd_submit_batch_registered( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
+                                        void const * const * sig, void const * const * pub, schar * err, ulong * tag,
+                                        ulong * ticket ) {
+  if( !e || !ticket || !n || !msg || !sz || !sig || !pub || !err ) return FD_ED25519_AMD_ERR_INVAL;
+  reg_view_t view;
+  if( !batch_registered_check( e, view, n, msg, sz, sig, pub ) ) return FD_ED25519_AMD_ERR_INVAL;
+  int rc;
+  slot_t * s = submit_slot( e, &rc );
+  if( !s ) return rc;
+  /* one chunk: the layout over the whole submission, into the free slot's scratch */
+  if( n > e->cap || fd_ed25519_amd_gather_layout( n, sz, e->cap, e->blob_cap, slot_gather_dst( e, s ) ) != n )
+    return FD_ED25519_AMD_ERR_INVAL;
+  return submit_run( e, s, ticket, [&]() -> long { return stage_batch_registered( e, s, view, n, msg, sz, sig, pub, err, tag ); } );
+}
+
+extern "C" int
+fd_ed25519_amd_submit_txns( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
+                            uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                            ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
+                            ulong * ticket ) {
+  if( !e || !ticket || !txn_cnt ) return FD_ED25519_AMD_ERR_INVAL;
+  int rc = txns_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag,
+                            desc_off, desc, desc_cap );
+  if( rc ) return rc;
+  slot_t * s = submit_slot( e, &rc );
+  if( !s ) return rc;
+  if( txns_chunk( e, txn_cnt, payload, txn_off, txn_sz ) != txn_cnt ) return FD_ED25519_AMD_ERR_INVAL;   /* one chunk */
+  s->a_dbase = 0UL;
+  txn_outs_t o = { txn_err, sig_err, txn_tag, sig_tag, desc_off, desc, desc_cap, &s->a_dbase };
+  ulong ns = 0;
+  rc = submit_run( e, s, ticket, [&]() -> long { return stage_txns( e, s, txn_cnt, payload, txn_off, txn_sz, o, &ns ); } );
+  /* pure host numbering: the one output a submit call writes */
+  if( !rc && sig_base ) fd_ed25519_amd_txn_slots( txn_cnt, payload, txn_off, txn_sz, sig_base );
+  return rc;
+}
+
+extern "C" int
+fd_ed25519_amd_submit_txns_registered( fd_ed25519_amd_t * e, ulong txn_cnt, void const * const * txn, ulong const * txn_sz,
+                                       schar * txn_err, uint * sig_base, schar * sig_err, ulong * txn_tag, ulong * sig_tag,
+                                       ulong * desc_off, uchar * desc, ulong desc_cap, ulong * ticket ) {
+  if( !e || !ticket || !txn_cnt || txn_cnt > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
+  if( txn_cnt > e->cap ) return FD_ED25519_AMD_ERR_INVAL;   /* one chunk (and it bounds the check's scratch) */
+  reg_view_t view;
+  std::vector<uint> slots( txn_cnt );
+  int rc = txns_registered_check( e, view, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, sig_tag, desc_off, desc,
+                                  desc_cap, slots.data() );
+  if( rc ) return rc;
+  slot_t * s = submit_slot( e, &rc );
+  if( !s ) return rc;
+  /* one chunk: the layout over the whole submission, into the free slot's scratch */
+  ulong ns = 0;
+  if( fd_ed25519_amd_txn_gather_layout( txn_cnt, txn_sz, slots.data(), e->cap, e->blob_cap, slot_gather_dst( e, s ), &ns ) != txn_cnt )
+    return FD_ED25519_AMD_ERR_INVAL;
+  s->a_dbase = 0UL;
+  txn_outs_t o = { txn_err, sig_err, txn_tag, sig_tag, desc_off, desc, desc_cap, &s->a_dbase };
+  rc = submit_run( e, s, ticket, [&]() -> long {
+    return stage_txns_registered( e, s, view, txn_cnt, txn, txn_sz, slots.data(), o, &ns );
+  } );
+  /* pure host numbering: the one output a submit call writes */
+  if( !rc && sig_base ) txns_sig_base( txn_cnt, slots.data(), sig_base );
+  return rc;
+}
+
+/* Deliver the oldest submission, if it has finished (block: wait for it). */
+static int
+async_deliver( fd_ed25519_amd_t * e, ulong * ticket, bool block ) {
+  if( !e || !ticket ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !e->a_cnt ) return FD_ED25519_AMD_ASYNC_NONE;
+  slot_t * s = &e->slot[e->a_head];
+  ulong const t = s->ticket;
+  int rc = FD_ED25519_AMD_OK;
+  if( !block ) {
+    if( !e->poll_event ) {
+      /* not finished yet: one load, no runtime call */
+      if( __atomic_load_n( s->h_tick, __ATOMIC_ACQUIRE ) != t ) return FD_ED25519_AMD_ASYNC_NONE;
+    } else {
+      hipError_t q = hipEventQuery( s->done );
+      if( q == hipErrorNotReady ) return FD_ED25519_AMD_ASYNC_NONE;
+      if( q != hipSuccess ) rc = FD_ED25519_AMD_ERR_DEVICE;
+    }
+  }
+  /* slot_drain waits for the slot's event whatever the word said: that wait
+     is the barrier the outputs' visibility rests on, cheap once the chunk has
+     finished.  It leaves the slot busy only when the runtime failed. */
+  if( !rc ) rc = slot_drain( s );
+  *ticket = t;
+  if( rc && s->busy ) return engine_quiesce( e, rc );
+  /* delivered, or the step guard tripped in this submission alone */
+  e->a_head = (e->a_head + 1) % e->nslot; e->a_cnt--;
+  return rc;
+}
+
+extern "C" int
+fd_ed25519_amd_async_poll( fd_ed25519_amd_t * e, ulong * ticket ) { return async_deliver( e, ticket, false ); }
+
+extern "C" int
+fd_ed25519_amd_async_wait( fd_ed25519_amd_t * e, ulong * ticket ) { return async_deliver( e, ticket, true ); }
+
+/* The engine's mode: every later call of this engine launches with it.  With
+   nothing in flight: the synchronous calls drain their chunks, and while
+   submissions are in flight the mode stays. */
 extern "C" int
 fd_ed25519_amd_set_mode( fd_ed25519_amd_t * e, int mode ) {
-  if( !e || !fd_amd_mode_ok( mode ) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !e || !fd_amd_mode_ok( mode ) || SYNC_REFUSED( e ) ) return FD_ED25519_AMD_ERR_INVAL;
   e->mode = mode;
   for( int k=0; k<FD_AMD_SLOT_MAX; k++ ) e->slot[k].strict = mode == FD_ED25519_AMD_MODE_STRICT;
   return FD_ED25519_AMD_OK;

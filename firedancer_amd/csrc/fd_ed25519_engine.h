@@ -1,5 +1,6 @@
 /* firedancer_amd/csrc/fd_ed25519_engine.h -- internal: the batch engine's
-   slots (one chunk in flight each; driven by fd_ed25519_engine.cpp alone),
+   slots (one chunk in flight each; driven by fd_ed25519_engine.cpp alone: by
+   run_ring for the synchronous calls, one at a time by the submit calls),
    the argument checks the multi-device engine shares with it, the NUMA
    helpers (fd_numa.cpp) and the transaction slot rule (fd_amd_txn_slots1,
    also the streaming tile's). */
@@ -63,6 +64,17 @@ struct slot_t {
   ulong * do_out; ulong do_n;
   uchar * d_out;  ulong d_cap;
   ulong * d_base;
+  /* asynchronous submissions (fd_ed25519_amd_submit_*): the ticket the slot
+     carries; its completion word, 8 bytes on a 64-byte line of their own in
+     mapped coherent pinned memory, to which k_ticket stores that ticket behind
+     the chunk's kernels (m_tick: its device address); tick_arm: the launch
+     under way is a submission that polls the word, so the slot's launch ends
+     with k_ticket; a_dbase: the descriptor byte base of a submission (always 0:
+     it is one chunk), what d_base points at */
+  ulong   ticket;
+  ulong * h_tick; void * m_tick;
+  int     tick_arm;
+  ulong   a_dbase;
 };
 
 /* What a transaction chunk's launch needs to return descriptors: where the
@@ -73,7 +85,7 @@ struct desc_req_t {
   ulong * off; uchar * desc; ulong cap; ulong * base; ulong bound;
 };
 
-#define FD_AMD_SLOT_MAX (16)
+#define FD_AMD_SLOT_MAX (FD_ED25519_AMD_SLOT_MAX)
 
 struct fd_ed25519_amd {
   int    device;
@@ -85,6 +97,16 @@ struct fd_ed25519_amd {
                         1 they go to d_pack by one H2D first (FD_ED25519_AMD_GATHER_COPY=1: the A/B of tools/batch_registered_cost.py) */
   int    gather_txn_waves; /* verify_txns_registered: wave cap of a throughput chunk's k_gather_txn, 64 (default), or
                               FD_ED25519_AMD_GATHER_TXN_WAVES in [1, 65536] (the A/B of tools/txns_registered_cost.py) */
+  /* asynchronous submissions: slots [0, nslot) taken round robin.  a_cnt in
+     flight, the oldest on slot a_head, the next goes to slot a_tail; ticket:
+     the last one handed out.  While a_cnt > 0 the synchronous calls refuse
+     (they would reuse the slots). */
+  ulong  ticket;
+  int    a_head, a_tail, a_cnt;
+  int    poll_event; /* 0 fd_ed25519_amd_async_poll reads the slot's completion word (default), 1 it asks
+                        hipEventQuery and no k_ticket is launched (FD_ED25519_AMD_ASYNC_POLL=event: the A/B of
+                        tools/async_cost.py) */
+  uint8_t * h_tickbuf; /* the slots' completion words, one allocation, 64 bytes each */
   slot_t slot[FD_AMD_SLOT_MAX];
 };
 

@@ -223,4 +223,9 @@ int fd_amd_launch_copy_out( void * d_dst_mapped, void const * d_src, size_t n, h
 int fd_amd_launch_tag_out( void * d_dst, void const * d_ws, size_t n, hipStream_t stream );
 int fd_amd_launch_tag_gather( void * d_dst, void const * d_ws, uint32_t txn_cnt, uint32_t const * d_tbase, hipStream_t stream );
 
+/* k_ticket (fd_ed25519_async.hip): one lane stores `ticket` to the 8-aligned
+   word at d_word (mapped host memory) with a system-scope release store, behind
+   whatever the stream holds. */
+int fd_amd_launch_ticket( void * d_word, uint64_t ticket, hipStream_t stream );
+
 #endif

@@ -175,6 +175,14 @@ def lib():
            "fd_txn_amd_parse_packed_scratch_footprint": ([ul], ul),
            "fd_ed25519_amd_verify_txns_desc": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp, vp, vp, ul], i),
            "fd_ed25519_amd_verify_txns_registered_desc": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, ul], i),
+           # asynchronous submissions
+           "fd_ed25519_amd_new_slots": ([i, ul, ul, ul], vp),
+           "fd_ed25519_amd_async_depth": ([vp], ul), "fd_ed25519_amd_async_in_flight": ([vp], ul),
+           "fd_ed25519_amd_submit_batch": ([vp, ul, vp, vp, vp, vp, vp, vp, c_ulong_p], i),
+           "fd_ed25519_amd_submit_batch_registered": ([vp, ul, vp, vp, vp, vp, vp, vp, c_ulong_p], i),
+           "fd_ed25519_amd_submit_txns": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp, vp, vp, ul, c_ulong_p], i),
+           "fd_ed25519_amd_submit_txns_registered": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, ul, c_ulong_p], i),
+           "fd_ed25519_amd_async_poll": ([vp, c_ulong_p], i), "fd_ed25519_amd_async_wait": ([vp, c_ulong_p], i),
            # the streaming tile's verdict mode
            "fd_verify_amd_tile_set_verdict_mode": ([vp, i], i), "fd_verify_amd_tile_verdict_mode": ([vp], i),
            # debug: k_dsmp's grid, the parked R'
@@ -287,6 +295,17 @@ class EngineError(RuntimeError):
     pass
 
 
+class EngineBusy(EngineError):
+    """FD_ED25519_AMD_ERR_BUSY: every slot of the engine carries a submission."""
+
+
+ERR_INVAL = -10      # FD_ED25519_AMD_ERR_INVAL
+ERR_DEVICE = -11     # FD_ED25519_AMD_ERR_DEVICE
+ERR_BUSY = -12       # FD_ED25519_AMD_ERR_BUSY
+ASYNC_NONE = 1       # FD_ED25519_AMD_ASYNC_NONE
+SLOT_MAX = 16        # FD_ED25519_AMD_SLOT_MAX
+
+
 MODE_REFERENCE = 0   # FD_ED25519_AMD_MODE_REFERENCE: the reference's verdicts, bit for bit (default)
 MODE_STRICT = 1      # FD_ED25519_AMD_MODE_STRICT: strict RFC 8032 (include/fd_ed25519_amd.h)
 
@@ -301,15 +320,22 @@ def _check_mode(mode):
 class Engine:
     """fd_ed25519_amd_t: one engine per device (multi-GPU = one per device).
     mode: MODE_REFERENCE (default) or MODE_STRICT, for every entry point of
-    this engine; set_mode changes it between batches."""
+    this engine; set_mode changes it between batches.  nslot: its slot count
+    (fd_ed25519_amd_new_slots, 2..SLOT_MAX), the depth of the submit_* /
+    poll / wait calls; None: fd_ed25519_amd_new's."""
 
-    def __init__(self, device=0, batch_max=1 << 16, blob_max=None, mode=MODE_REFERENCE):
+    def __init__(self, device=0, batch_max=1 << 16, blob_max=None, mode=MODE_REFERENCE, nslot=None):
         _check_mode(mode)
+        self._h = None
+        self._pending = {}   # ticket -> (outputs of the delivered submission, what must stay alive until then)
         if blob_max is None:
             blob_max = max(batch_max * 256, MSG_MAX)
-        self._h = lib().fd_ed25519_amd_new(int(device), int(batch_max), int(blob_max))
+        if nslot is None:
+            self._h = lib().fd_ed25519_amd_new(int(device), int(batch_max), int(blob_max))
+        else:
+            self._h = lib().fd_ed25519_amd_new_slots(int(device), int(batch_max), int(blob_max), int(nslot))
         if not self._h:
-            raise EngineError("fd_ed25519_amd_new(device=%d) failed (no HIP device?)" % device)
+            raise EngineError("fd_ed25519_amd_new(device=%d) failed (no HIP device, or a bad slot count?)" % device)
         self.device = device
         if mode != MODE_REFERENCE:
             self.set_mode(mode)
@@ -324,15 +350,136 @@ class Engine:
         return int(lib().fd_ed25519_amd_mode(self._h))
 
     def close(self):
+        """fd_ed25519_amd_delete: waits for the submissions in flight and
+        delivers none of them."""
         if self._h:
             lib().fd_ed25519_amd_delete(self._h)
             self._h = None
+            self._pending.clear()
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+    # ------------------------------------------------------------ asynchronous submissions
+
+    @property
+    def async_depth(self):
+        """fd_ed25519_amd_async_depth: submissions the engine keeps in flight (its slot count)."""
+        return int(lib().fd_ed25519_amd_async_depth(self._h))
+
+    @property
+    def in_flight(self):
+        """fd_ed25519_amd_async_in_flight."""
+        return int(lib().fd_ed25519_amd_async_in_flight(self._h))
+
+    def _submitted(self, name, rc, ticket, finish, keep):
+        if rc == ERR_BUSY:
+            raise EngineBusy("%s: %d submissions in flight" % (name, self.in_flight))
+        if rc:
+            if not self.in_flight:        # a device error dropped what was in flight
+                self._pending.clear()
+            raise EngineError("%s rc=%d" % (name, rc))
+        self._pending[int(ticket.value)] = (finish, keep)
+        return int(ticket.value)
+
+    def submit_batch_ptrs(self, pub_ptr, sig_ptr, msg_ptr, msg_sz, want_tags=False, registered=True):
+        """fd_ed25519_amd_submit_batch_registered (registered=False:
+        fd_ed25519_amd_submit_batch, which copies the bytes behind the
+        pointers before it returns): verify_batch_ptrs as one chunk, launched
+        now and delivered by poll() / wait().  Returns the ticket; raises
+        EngineBusy with async_depth submissions in flight, EngineError when the
+        batch is empty or exceeds one chunk.  Registered: the bytes behind the
+        pointers must stay valid until delivery."""
+        pp = np.ascontiguousarray(pub_ptr, np.uint64)
+        sp = np.ascontiguousarray(sig_ptr, np.uint64)
+        mp = np.ascontiguousarray(msg_ptr, np.uint64)
+        sz = np.ascontiguousarray(msg_sz, np.uint64)
+        n = int(pp.size)
+        assert sp.size == n and mp.size == n and sz.size == n
+        err = np.zeros(max(n, 1), np.int8)
+        tags = np.zeros(max(n, 1), np.uint64) if want_tags else None
+        name = "fd_ed25519_amd_submit_batch_registered" if registered else "fd_ed25519_amd_submit_batch"
+        t = ctypes.c_ulong(0)
+        rc = getattr(lib(), name)(self._h, n, _ptr(mp), _ptr(sz), _ptr(sp), _ptr(pp), _ptr(err),
+                                  _ptr(tags) if want_tags else None, ctypes.byref(t))
+        return self._submitted(name, rc, t, lambda: (err[:n], tags[:n]) if want_tags else err[:n],
+                               (pub_ptr, sig_ptr, msg_ptr) if registered else None)
+
+    def submit_batch(self, msgs, sigs, pubs, want_tags=False):
+        """verify_batch (lists of bytes-like) as a submission: staged, every
+        byte copied before it returns.  Returns the ticket."""
+        n = len(msgs)
+        keep = [bytes(m) for m in msgs] + [bytes(s) for s in sigs] + [bytes(p) for p in pubs]
+        bufs = [ctypes.create_string_buffer(b, max(len(b), 1)) for b in keep]
+        addr = np.array([ctypes.addressof(b) for b in bufs], np.uint64)
+        return self.submit_batch_ptrs(addr[2 * n:], addr[n:2 * n], addr[:n], [len(b) for b in keep[:n]],
+                                      want_tags=want_tags, registered=False)
+
+    def submit_txns_ptrs(self, txn_ptr, txn_sz, want_sigs=False, want_tags=False, want_desc=False, registered=True):
+        """fd_ed25519_amd_submit_txns_registered: verify_txns_ptrs as one
+        chunk, launched now and delivered by poll() / wait(); the payloads must
+        stay valid until then.  registered=False: the payloads are copied here
+        and go through fd_ed25519_amd_submit_txns (submit_txns).  Returns the
+        ticket."""
+        tp = np.ascontiguousarray(txn_ptr, np.uint64)
+        sz = np.ascontiguousarray(txn_sz, np.uint64)
+        n = int(tp.size)
+        assert sz.size == n
+        if ((tp == 0) & (sz != 0)).any():
+            raise EngineError("submit_txns_ptrs: NULL payload pointer with a size")
+        if not registered:
+            pays = [ctypes.string_at(int(p), int(z)) if z else b"" for p, z in zip(tp.tolist(), sz.tolist())]
+            off = np.concatenate(([0], np.cumsum(sz)[:-1])).astype(np.uint32) if n else np.zeros(0, np.uint32)
+            return self.submit_txns(np.frombuffer(b"".join(pays), np.uint8), off, sz.astype(np.uint32),
+                                    want_sigs=want_sigs, want_tags=want_tags, want_desc=want_desc)
+        base, tot = txn_slots_ptrs(tp, sz) if (want_sigs or want_tags) else (None, 0)
+        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc)
+        t = ctypes.c_ulong(0)
+        rc = lib().fd_ed25519_amd_submit_txns_registered(self._h, n, _ptr(tp), _ptr(sz), *o.args(), ctypes.byref(t))
+        return self._submitted("fd_ed25519_amd_submit_txns_registered", rc, t, o.result, txn_ptr)
+
+    def submit_txns(self, payload, txn_off, txn_sz, want_sigs=False, want_tags=False, want_desc=False):
+        """fd_ed25519_amd_submit_txns: verify_txns as one chunk, the payload
+        bytes copied before it returns, delivered by poll() / wait().  Returns
+        the ticket."""
+        payload = np.ascontiguousarray(payload, np.uint8)
+        off = np.ascontiguousarray(txn_off, np.uint32)
+        sz = np.ascontiguousarray(txn_sz, np.uint32)
+        n = int(off.size)
+        base, tot = txn_slots(payload, off, sz) if (want_sigs or want_tags) else (None, 0)
+        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc)
+        t = ctypes.c_ulong(0)
+        rc = lib().fd_ed25519_amd_submit_txns(self._h, n, _ptr(payload), _ptr(off), _ptr(sz), int(payload.size), *o.args(),
+                                              ctypes.byref(t))
+        return self._submitted("fd_ed25519_amd_submit_txns", rc, t, o.result, None)
+
+    def _collect(self, name):
+        t = ctypes.c_ulong(0)
+        rc = getattr(lib(), name)(self._h, ctypes.byref(t))
+        if rc == ASYNC_NONE:
+            return None
+        finish, _ = self._pending.pop(int(t.value), (None, None))
+        if rc:
+            if not self.in_flight:        # a runtime error dropped every submission in flight
+                self._pending.clear()
+            raise EngineError("%s rc=%d (ticket %d)" % (name, rc, t.value))
+        return int(t.value), finish() if finish else None    # None: submitted through the C call directly
+
+    def poll(self):
+        """fd_ed25519_amd_async_poll: None when nothing is in flight or the
+        oldest submission has not finished; else (ticket, outputs), outputs
+        being what the synchronous method returns.  Never blocks."""
+        return self._collect("fd_ed25519_amd_async_poll")
+
+    def wait(self):
+        """fd_ed25519_amd_async_wait: poll() that blocks for the oldest
+        submission; None only when nothing is in flight."""
+        return self._collect("fd_ed25519_amd_async_wait")
+
+    # ------------------------------------------------------------ synchronous calls
 
     def verify_soa(self, pub, sig, msg_off, msg_sz, blob, want_tags=False):
         """want_tags: returns (err, tag), tag uint64 (n,): the dedup tags
@@ -495,6 +642,36 @@ class Engine:
         base = np.uint64(arena.ctypes.data)
         return self.verify_txns_ptrs(base + np.asarray(txn_off, np.uint64), txn_sz, want_sigs=want_sigs,
                                      want_tags=want_tags, want_desc=want_desc)
+
+
+class _TxnOutputs:
+    """The output arrays of one transaction submission, alive until it is
+    delivered: args() is the (txn_err .. desc_cap) run of the submit calls'
+    arguments, result() what verify_txns returns once they are filled."""
+
+    def __init__(self, n, txn_sz, base, tot, want_sigs, want_tags, want_desc):
+        self.n, self.base, self.want = n, base, (want_sigs, want_tags, want_desc)
+        self.terr = np.zeros(max(n, 1), np.int8)
+        self.serr = np.zeros(max(tot, 1), np.int8) if want_sigs else None
+        self.ttag = np.zeros(max(n, 1), np.uint64) if want_tags else None
+        self.stag = np.zeros(max(tot, 1), np.uint64) if want_tags else None
+        self.doff, self.desc = _desc_buffers(txn_sz) if want_desc else (None, None)
+
+    def args(self):
+        p = lambda a: _ptr(a) if a is not None else None
+        return (p(self.terr), p(self.base), p(self.serr), p(self.ttag), p(self.stag), p(self.doff), p(self.desc),
+                int(self.desc.size) if self.desc is not None else 0)
+
+    def result(self):
+        want_sigs, want_tags, want_desc = self.want
+        out = (self.terr[:self.n],)
+        if want_sigs:
+            out += (self.base, self.serr[:int(self.base[-1])])
+        if want_tags:
+            out += (self.ttag[:self.n], self.stag[:int(self.base[-1])])
+        if want_desc:
+            out += (self.doff, self.desc[:int(self.doff[-1])])
+        return out if len(out) > 1 else out[0]
 
 
 def txn_desc_bound(sz):

@@ -129,6 +129,9 @@ fd_ed25519_sign( void *        sig,
 #define FD_ED25519_AMD_OK          ( 0)
 #define FD_ED25519_AMD_ERR_INVAL   (-10) /* bad argument (NULL, n too large, a message larger than the engine's blob_max) */
 #define FD_ED25519_AMD_ERR_DEVICE  (-11) /* HIP error / no device */
+#define FD_ED25519_AMD_ERR_BUSY    (-12) /* a submit call: every slot of the engine carries a submission */
+#define FD_ED25519_AMD_ASYNC_NONE  ( 1)  /* async_poll / async_wait: nothing to deliver (not an error) */
+#define FD_ED25519_AMD_SLOT_MAX    (16)  /* most slots (chunks in flight) an engine can have */
 
 /* Solana MTU: the message size the staging is dimensioned
    for.  Longer messages verify too, as long as each fits the engine's
@@ -146,6 +149,14 @@ typedef struct fd_ed25519_amd fd_ed25519_amd_t;
    2, or FD_ED25519_AMD_NSLOT (2..6) from the environment. */
 fd_ed25519_amd_t *
 fd_ed25519_amd_new( int device, ulong batch_max, ulong blob_max );
+
+/* fd_ed25519_amd_new with the slot count as an argument: slots in
+   [2, FD_ED25519_AMD_SLOT_MAX], NULL otherwise (checked before anything
+   touches a device).  fd_ed25519_amd_new is this call with 2, or
+   FD_ED25519_AMD_NSLOT.  The slot count is the engine's depth for the
+   asynchronous calls below. */
+fd_ed25519_amd_t *
+fd_ed25519_amd_new_slots( int device, ulong batch_max, ulong blob_max, ulong slots );
 
 void
 fd_ed25519_amd_delete( fd_ed25519_amd_t * eng );
@@ -435,6 +446,123 @@ fd_ed25519_amd_multi_verify_soa_tag( fd_ed25519_amd_multi_t * multi,
                                      ulong                    blob_sz,
                                      schar *                  err,
                                      ulong *                  tag );
+
+/* ===== Asynchronous submissions =====
+
+   Every batch call above returns when its last chunk has been delivered; a
+   caller with a run loop of its own is stuck inside the call for the whole
+   GPU round trip.  The submit calls launch ONE chunk on one of the engine's
+   slots and return; fd_ed25519_amd_async_poll / fd_ed25519_amd_async_wait
+   deliver finished submissions later.  One thread can so keep
+   fd_ed25519_amd_async_depth( eng ) submissions in flight (the engine's slot
+   count: fd_ed25519_amd_new_slots) and do its other work in between.
+
+   Each submit call takes the arguments of the most general synchronous call
+   of its family plus `ticket`:
+     fd_ed25519_amd_submit_batch             fd_ed25519_amd_verify_batch_tag
+     fd_ed25519_amd_submit_batch_registered  fd_ed25519_amd_verify_batch_registered_tag
+     fd_ed25519_amd_submit_txns              fd_ed25519_amd_verify_txns_desc            (fd_txn_amd.h)
+     fd_ed25519_amd_submit_txns_registered   fd_ed25519_amd_verify_txns_registered_desc (fd_txn_amd.h)
+   Optional outputs are NULL exactly as in the synchronous call.
+
+   One chunk per submission.  A submission must fit the chunk the matching
+   synchronous call would cut first: for the registered forms,
+   fd_ed25519_amd_gather_layout / fd_ed25519_amd_txn_gather_layout over the
+   whole submission returns n; for the staged forms, the count (batch_max),
+   signature-slot (batch_max, transactions) and byte (blob_max, unpadded) caps
+   of their chunk loops hold for the whole submission.  Otherwise, and for
+   n == 0 or ticket == NULL, the submit returns FD_ED25519_AMD_ERR_INVAL.
+   Every argument check of the synchronous call applies unchanged, the
+   registration table and the descriptor bound included.  On any error return
+   nothing is launched, no output is touched, no ticket is consumed and
+   *ticket is untouched.
+
+   Tickets are per engine: 1, 2, 3, ..., one per accepted submission.
+   Submissions take the slots round robin.
+
+   Busy.  With fd_ed25519_amd_async_depth submissions in flight a submit
+   returns FD_ED25519_AMD_ERR_BUSY, with the effect of an error return.  (A
+   full engine says BUSY before the one-chunk rule is looked at; the argument
+   checks come first.)
+
+   Inputs.  The staged forms copy every input byte during the submit call: the
+   caller may reuse or free msg, sig, pub, payload and the index arrays as
+   soon as it returns.  The registered forms read the caller's memory until
+   delivery: the pointed-to bytes and the registration must stay valid until
+   then; the pointer and size arrays themselves are consumed during submit.
+
+   Outputs are written only inside async_poll / async_wait, by the call that
+   reports the ticket; until then the caller's output arrays are not touched.
+   The one exception is sig_base, pure host numbering, written by the submit
+   call.  Outputs are byte for byte those of the synchronous call for the same
+   arguments, in the verdict mode the engine had at submit.  Descriptor
+   offsets are relative to the submission: desc_off[0] == 0.
+
+   Delivery is in ticket order, one submission per call.
+   fd_ed25519_amd_async_poll never blocks: with nothing in flight, or the
+   oldest submission not finished, it returns FD_ED25519_AMD_ASYNC_NONE and
+   leaves *ticket alone; when the oldest has finished it delivers it, sets
+   *ticket and returns FD_ED25519_AMD_OK -- or FD_ED25519_AMD_ERR_DEVICE when
+   that submission hit k_dsmp's step guard (below): its outputs are then
+   unspecified, and younger submissions are unaffected.
+   fd_ed25519_amd_async_wait is the same but blocks for the oldest; it returns
+   ASYNC_NONE only when nothing is in flight.  On a HIP runtime error the call
+   returns FD_ED25519_AMD_ERR_DEVICE with the oldest ticket, every submission
+   in flight is dropped (their outputs are never written) and
+   fd_ed25519_amd_async_in_flight becomes 0.
+
+   "Not finished yet" costs one load: the last kernel of a submission
+   (k_ticket) stores its ticket into a word of mapped host memory and
+   async_poll compares that word; no HIP call is made until it matches.
+   Delivery itself still waits for the slot's HIP event, so the outputs never
+   depend on the order in which the word and the results become visible.
+   FD_ED25519_AMD_ASYNC_POLL=event in the environment when the engine is
+   created makes async_poll ask hipEventQuery instead and launches no
+   k_ticket (the A/B of tools/async_cost.py).
+
+   Mixing.  While fd_ed25519_amd_async_in_flight( eng ) > 0 every synchronous
+   batch call of that engine and fd_ed25519_amd_set_mode return
+   FD_ED25519_AMD_ERR_INVAL and touch nothing: they would reuse the slots.
+   fd_ed25519_amd_delete waits for what is in flight and delivers nothing.
+   The rule stays one engine per host thread: submit, poll and wait of one
+   engine come from one thread.
+
+   Out of scope: the SoA shapes (a caller who holds a whole SoA batch gains
+   nothing from submitting it in pieces), the multi-device engine, the
+   drop-in fd_ed25519_verify and the streaming tile. */
+ulong
+fd_ed25519_amd_async_depth( fd_ed25519_amd_t const * eng );
+
+ulong
+fd_ed25519_amd_async_in_flight( fd_ed25519_amd_t const * eng );
+
+int
+fd_ed25519_amd_submit_batch( fd_ed25519_amd_t *   eng,
+                             ulong                n,
+                             void const * const * msg,
+                             ulong const *        sz,
+                             void const * const * sig,
+                             void const * const * pub,
+                             schar *              err,
+                             ulong *              tag,
+                             ulong *              ticket );
+
+int
+fd_ed25519_amd_submit_batch_registered( fd_ed25519_amd_t *   eng,
+                                        ulong                n,
+                                        void const * const * msg,
+                                        ulong const *        sz,
+                                        void const * const * sig,
+                                        void const * const * pub,
+                                        schar *              err,
+                                        ulong *              tag,
+                                        ulong *              ticket );
+
+int
+fd_ed25519_amd_async_poll( fd_ed25519_amd_t * eng, ulong * ticket );
+
+int
+fd_ed25519_amd_async_wait( fd_ed25519_amd_t * eng, ulong * ticket );
 
 /* Device-resident batch: every pointer is HIP device memory, already
    resident (the layout of fd_ed25519_amd_verify_soa).  Enqueues the

@@ -415,6 +415,54 @@ fd_ed25519_amd_verify_txns_registered_desc( fd_ed25519_amd_t *   eng,
                                             uchar *              desc,
                                             ulong                desc_cap );
 
+/* Asynchronous submissions of the two calls above: one chunk on one slot,
+   launched now and delivered later by fd_ed25519_amd_async_poll /
+   fd_ed25519_amd_async_wait.  The contract is "Asynchronous submissions" in
+   fd_ed25519_amd.h; what is particular to transactions:
+   - one chunk: the staged form's transactions number at most batch_max,
+     their signature slots (fd_ed25519_amd_txn_slots) total at most batch_max
+     and their bytes at most blob_max; for the registered form
+     fd_ed25519_amd_txn_gather_layout over the whole submission returns
+     txn_cnt.  Otherwise, and for txn_cnt == 0, FD_ED25519_AMD_ERR_INVAL;
+   - sig_base (when given) is written by the submit call, every other output
+     at delivery; txn_tag, sig_tag, sig_err, desc_off / desc are optional as
+     in the synchronous calls;
+   - desc_off is relative to the submission (desc_off[0] == 0) and desc_cap
+     is checked against the submission's bound sum;
+   - the staged form copies the payload bytes during submit; the registered
+     form's payloads are read until delivery. */
+int
+fd_ed25519_amd_submit_txns( fd_ed25519_amd_t * eng,
+                            ulong              txn_cnt,
+                            uchar const *      payload,
+                            uint const *       txn_off,
+                            uint const *       txn_sz,
+                            ulong              payload_sz,
+                            schar *            txn_err,
+                            uint *             sig_base,
+                            schar *            sig_err,
+                            ulong *            txn_tag,
+                            ulong *            sig_tag,
+                            ulong *            desc_off,
+                            uchar *            desc,
+                            ulong              desc_cap,
+                            ulong *            ticket );
+
+int
+fd_ed25519_amd_submit_txns_registered( fd_ed25519_amd_t *   eng,
+                                       ulong                txn_cnt,
+                                       void const * const * txn,
+                                       ulong const *        txn_sz,
+                                       schar *              txn_err,
+                                       uint *               sig_base,
+                                       schar *              sig_err,
+                                       ulong *              txn_tag,
+                                       ulong *              sig_tag,
+                                       ulong *              desc_off,
+                                       uchar *              desc,
+                                       ulong                desc_cap,
+                                       ulong *              ticket );
+
 /* Signature-slot numbering of a pointer-array batch (pure host code, no
    device): the rule of fd_ed25519_amd_txn_slots, one payload per pointer.
    txn[t] is not looked at when txn_sz[t] is 0, and a NULL txn[t] reserves
