@@ -239,55 +239,54 @@ slot_tags( slot_t * s, ulong n ) {
   return fd_amd_launch_tag_out( s->m_tag, s->d_ws, n, s->stream ) ? FD_ED25519_AMD_ERR_DEVICE : FD_ED25519_AMD_OK;
 }
 
+/* Forget the chunk in flight on s: where its outputs were to go, and that
+   there is one.  A slot that is not busy has an all-zero record. */
+static void
+slot_forget( slot_t * s ) {
+  memset( &s->fl, 0, sizeof(s->fl) );
+  s->busy = 0;
+}
+
 /* Wait for a slot's chunk and deliver its verdicts and, where the caller
-   asked for them, its tags: one place, so that draining a slot before it is
-   reused covers both outputs. */
+   asked for them, its tags and descriptors: one place, so that draining a
+   slot before it is reused covers every output. */
 static int
 slot_drain( slot_t * s ) {
   if( !s->busy ) return FD_ED25519_AMD_OK;
   HIPCHK( hipEventSynchronize( s->done ) );
+  slot_flight_t const & f = s->fl;
   /* k_dsmp's hang guard marks every verdict of its launch (k_fin) */
-  bool fault = ( s->chk_err  && s->h_err[0] == (int8_t)FD_AMD_VERDICT_DEVICE ) ||
-               ( s->chk_terr && memchr( s->h_terr, (uint8_t)FD_AMD_VERDICT_DEVICE, s->chk_terr ) );
+  bool fault = ( f.chk_err  && s->h_err[0] == (int8_t)FD_AMD_VERDICT_DEVICE ) ||
+               ( f.chk_terr && memchr( s->h_terr, (uint8_t)FD_AMD_VERDICT_DEVICE, f.chk_terr ) );
   if( fault ) fprintf( stderr, "fd_ed25519_amd: the pooled double-scalar multiply hit its step guard\n" );
   /* descriptors: the chunk's total is known only now.  The callers' bound
      check keeps both conditions from ever holding; they are the backstop that
      keeps the copy below inside the staging and the caller's buffer */
-  else if( s->do_out && ( s->h_doff[s->do_n] > s->desc_stage || *s->d_base + s->h_doff[s->do_n] > s->d_cap ) ) {
+  else if( f.do_out && ( s->h_doff[f.do_n] > s->desc_stage || *f.d_base + s->h_doff[f.do_n] > f.d_cap ) ) {
     fprintf( stderr, "fd_ed25519_amd: a chunk's descriptors exceed their bound\n" );
     fault = true;
   } else {
-    if( s->out   ) memcpy( s->out,   s->h_err,  s->n );
-    if( s->t_out ) memcpy( s->t_out, s->h_terr, s->t_n );
-    if( s->s_out ) memcpy( s->s_out, s->h_err,  s->s_n );
-    if( s->g_out  ) memcpy( s->g_out,  s->h_tag,  8UL*s->g_n );
-    if( s->tg_out ) memcpy( s->tg_out, s->h_ttag, 8UL*s->tg_n );
-    if( s->do_out ) {   /* chunk-relative offsets -> the batch's numbering; the bytes behind the earlier chunks' */
-      ulong const base = *s->d_base, tot = s->h_doff[s->do_n];
-      for( ulong j=0; j<=s->do_n; j++ ) s->do_out[j] = base + s->h_doff[j];
-      if( tot ) memcpy( s->d_out + base, s->h_desc, tot );
-      *s->d_base = base + tot;
+    for( int k=0; k<f.ncp; k++ ) memcpy( f.cp[k].dst, f.cp[k].src, f.cp[k].sz );
+    if( f.do_out ) {   /* chunk-relative offsets -> the batch's numbering; the bytes behind the earlier chunks' */
+      ulong const base = *f.d_base, tot = s->h_doff[f.do_n];
+      for( ulong j=0; j<=f.do_n; j++ ) f.do_out[j] = base + s->h_doff[j];
+      if( tot ) memcpy( f.d_out + base, s->h_desc, tot );
+      *f.d_base = base + tot;
     }
   }
-  s->out = s->t_out = s->s_out = NULL;
-  s->g_out = s->tg_out = NULL;
-  s->do_out = NULL;
-  s->busy = 0;
+  slot_forget( s );
   return fault ? FD_ED25519_AMD_ERR_DEVICE : FD_ED25519_AMD_OK;
 }
 
 /* Error exit of a batch call: wait for every chunk still in flight and
-   forget where its verdicts and tags were to go, so no later call writes
-   into the caller's (by then possibly freed) output arrays. */
+   forget where its verdicts, tags and descriptors were to go, so no later
+   call writes into the caller's (by then possibly freed) output arrays. */
 static int
 engine_quiesce( fd_ed25519_amd_t * e, int rc ) {
   for( int k=0; k<FD_AMD_SLOT_MAX; k++ ) {
     slot_t * s = &e->slot[k];
     if( s->busy ) (void)hipEventSynchronize( s->done );
-    s->out = s->t_out = s->s_out = NULL;
-    s->g_out = s->tg_out = NULL;
-    s->do_out = NULL;
-    s->busy = 0;
+    slot_forget( s );
   }
   e->a_cnt = 0; e->a_head = e->a_tail;   /* every submission in flight is dropped */
   return rc;
@@ -303,14 +302,50 @@ slot_done( slot_t * s ) {
   return FD_ED25519_AMD_OK;
 }
 
-/* The chunk just launched on s is in flight: n verdicts, written to h_err,
-   go to `out` when the slot is drained; with tag != NULL its n tags, written
-   to h_tag, go to `tag`. */
+/* When the chunk being launched on s is drained, `sz` bytes of the slot's
+   staging at src go to the caller's dst (NULL: not asked for). */
 static void
-slot_in_flight( slot_t * s, schar * out, ulong * tag, ulong n ) {
-  s->out = out; s->n = n; s->busy = 1;
-  s->chk_err = n; s->chk_terr = 0;
-  s->g_out = tag; s->g_n = n;
+slot_deliver( slot_t * s, void * dst, void const * src, ulong sz ) {
+  if( dst ) s->fl.cp[s->fl.ncp++] = { dst, src, sz };
+}
+
+/* The five planes a chunk's verify kernels read, as the device sees them. */
+struct planes_t { uint8_t const * pub; uint8_t const * sig; uint32_t const * off; uint32_t const * sz; uint8_t const * blob; };
+
+static inline planes_t
+slot_planes( slot_t const * s ) { return planes_t{ s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_blob }; }
+
+/* The verify launch of every engine slot, into the slot's d_err and
+   workspace on its stream, in the engine's mode.  skip and out: as
+   fd_amd_launch_verify's d_skip and d_out. */
+static int
+slot_verify( slot_t * s, ulong n, planes_t const & p, int want_stats, int8_t const * skip, void * out ) {
+  return fd_amd_launch_verify( (uint32_t)n, p.pub, p.sig, p.off, p.sz, p.blob, s->d_err, s->d_ws, s->stream, want_stats, NULL,
+                               skip, 0, (int8_t *)out, s->strict ) ? FD_ED25519_AMD_ERR_DEVICE : FD_ED25519_AMD_OK;
+}
+
+/* The launch tail of every signature chunk: n signatures whose planes p are
+   on the device (or on their way there on the slot's stream, or mapped) are
+   verified; the n verdicts, written to h_err, go to `err` when the slot is
+   drained; with tag != NULL the n tags, written to h_tag, go to `tag`. */
+static int
+slot_launch_sig( slot_t * s, ulong n, planes_t const & p, schar * err, ulong * tag ) {
+  /* latency path: the DSM kernel (strict mode: k_strict) writes the verdicts
+     into the mapped h_err itself */
+  bool const lat = fd_amd_uses_latency_path( (uint32_t)n, 0 ) != 0;
+  if( slot_verify( s, n, p, 1, NULL, lat ? s->m_err : NULL ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  if( !lat ) HIPCHK( slot_out( s, s->m_err, s->d_err, n ) );
+  /* latency path: k_tag_out after the DSM kernel.  The stream is in order
+     and the host waits for one event behind both outputs, so either side of
+     the DSM kernel costs the same one launch; after it, the verify launch
+     sequence is the untagged call's */
+  if( tag && slot_tags( s, n ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  if( slot_done( s ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  slot_deliver( s, err, s->h_err, n );
+  slot_deliver( s, tag, s->h_tag, 8UL*n );
+  s->fl.chk_err = n;
+  s->busy = 1;
+  return FD_ED25519_AMD_OK;
 }
 
 /* Chunk of n signatures staged in s->h_pack as [pub 32n | sig 64n | off 4n | sz 4n | blob]. */
@@ -324,83 +359,77 @@ slot_launch_packed( slot_t * s, ulong n, ulong blob_sz, schar * out, ulong * tag
     d = s->d_pack;
     HIPCHK( hipMemcpyAsync( d, s->h_pack, 104UL*n + blob_sz, hipMemcpyHostToDevice, s->stream ) );
   }
-  bool const lat = fd_amd_uses_latency_path( (uint32_t)n, 0 ) != 0;
-  if( fd_amd_launch_verify( (uint32_t)n, d, d + 32UL*n, (uint32_t *)(d + 96UL*n), (uint32_t *)(d + 100UL*n),
-                            d + 104UL*n, s->d_err, s->d_ws, s->stream, 1, NULL, NULL, 0,
-                            lat ? (int8_t *)s->m_err : NULL, s->strict ) )   /* latency path: verdicts written in place */
+  return slot_launch_sig( s, n, planes_t{ d, d + 32UL*n, (uint32_t *)(d + 96UL*n), (uint32_t *)(d + 100UL*n), d + 104UL*n },
+                          out, tag );
+}
+
+/* Where one transaction chunk's outputs go: the caller's arrays at the
+   chunk's first transaction (txn_err, txn_tag, desc_off) and first signature
+   slot (sig_err, sig_tag), NULL where not asked for; the whole descriptor
+   buffer, and the call's running descriptor byte base. */
+struct txn_outs_t {
+  schar * txn_err; schar * sig_err; ulong * txn_tag; ulong * sig_tag;
+  ulong * desc_off; uchar * desc; ulong desc_cap; ulong * dbase;
+};
+
+/* The kernels of a transaction chunk whose payloads and planes (d_blob,
+   d_toff, d_tsz, d_tbase[0..c]) are on the device, or on their way there on
+   the slot's stream: parse, verify with d_skip, reduce, outputs, tags,
+   descriptors.  c transactions, nslot = d_tbase[c] signature slots.
+   Per-transaction verdicts land in h_terr, per-signature ones (when
+   o.sig_err) in h_err; the per-transaction tags (when o.txn_tag) in h_ttag,
+   the per-signature ones (when o.sig_tag) in h_tag; with o.desc_off the
+   chunk's descriptors, packed, in h_desc and their chunk-relative offsets in
+   h_doff[0..c] (desc_bound: the sum of fd_txn_amd_desc_bound over the
+   chunk). */
+static int
+slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, txn_outs_t const & o, ulong desc_bound ) {
+  if( fd_amd_launch_txn_parse( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, s->d_fp, NULL, 0, s->d_tbase,
+                               s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_skip, s->stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
-  if( !lat ) HIPCHK( slot_out( s, s->m_err, s->d_err, n ) );
-  /* latency path: k_tag_out after the DSM kernel.  The stream is in order
-     and the host waits for one event behind both outputs, so either side of
-     the DSM kernel costs the same one launch; after it, the verify launch
-     sequence is the untagged call's */
-  if( tag && slot_tags( s, n ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  if( nslot && slot_verify( s, nslot, slot_planes( s ), 0, s->d_skip, NULL ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  /* after k_strict (same stream): a transaction's verdict is its first failing signature's code in the engine's mode */
+  if( fd_amd_launch_txn_reduce( (uint32_t)c, s->d_fp, s->d_tbase, s->d_err, s->d_terr, s->stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  HIPCHK( slot_out( s, s->m_terr, s->d_terr, c ) );
+  if( o.sig_err && nslot ) HIPCHK( slot_out( s, s->m_err, s->d_err, nslot ) );
+  /* tags: per transaction its first slot's (no slot launched: no workspace is read), per signature the plane */
+  if( o.txn_tag && fd_amd_launch_tag_gather( s->m_ttag, s->d_ws, (uint32_t)c, s->d_tbase, s->stream ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  if( o.sig_tag && nslot && slot_tags( s, nslot ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  /* descriptors: packed in HBM from the footprints k_txn_parse left (0 where
+     it rejected the payload, the fail-closed slot mismatch included), then
+     one coalesced copy-out that reads the chunk's total on the device: the
+     host learns it from h_doff[c] when it drains the slot, without a sync */
+  if( o.desc_off ) {
+    if( fd_amd_launch_txn_pack( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, s->d_fp, s->d_dbsum, s->d_doff, s->d_desc,
+                                s->desc_stage, s->stream ) ||
+        fd_amd_launch_desc_out( s->m_desc, s->d_desc, s->m_doff, s->d_doff, (uint32_t)c, s->desc_stage, desc_bound, s->stream ) )
+      return FD_ED25519_AMD_ERR_DEVICE;
+  }
   if( slot_done( s ) ) return FD_ED25519_AMD_ERR_DEVICE;
-  slot_in_flight( s, out, tag, n );
+  slot_deliver( s, o.txn_err, s->h_terr, c );
+  slot_deliver( s, o.txn_tag, s->h_ttag, 8UL*c );
+  if( nslot ) {
+    slot_deliver( s, o.sig_err, s->h_err, nslot );
+    slot_deliver( s, o.sig_tag, s->h_tag, 8UL*nslot );
+  }
+  s->fl.chk_err = (o.sig_err && nslot) ? nslot : 0; s->fl.chk_terr = c;
+  s->fl.do_out = o.desc_off; s->fl.do_n = c;
+  s->fl.d_out = o.desc; s->fl.d_cap = o.desc_cap; s->fl.d_base = o.dbase;
+  s->busy = 1;
   return FD_ED25519_AMD_OK;
 }
 
 /* Launch a staged transaction chunk: c transactions (payload bytes in
    h_blob, rebased offsets in h_toff/h_tsz, signature-slot bases in
-   h_tbase[0..c]), nslot = h_tbase[c] signature slots.  Per-transaction
-   verdicts land in h_terr, per-signature ones (when s_out) in h_err; the
-   per-transaction tags (when tt_out) in h_ttag, the per-signature ones (when
-   st_out) in h_tag; with dq != NULL the chunk's descriptors, packed, in
-   h_desc and their chunk-relative offsets in h_doff[0..c]. */
-static int slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, schar * t_out, schar * s_out, ulong * tt_out, ulong * st_out,
-                                desc_req_t const * dq );
-
+   h_tbase[0..c]), nslot = h_tbase[c] signature slots. */
 static int
-slot_launch_txn( slot_t * s, ulong c, ulong nslot, ulong blob_sz, schar * t_out, schar * s_out, ulong * tt_out,
-                 ulong * st_out, desc_req_t const * dq ) {
+slot_launch_txn( slot_t * s, ulong c, ulong nslot, ulong blob_sz, txn_outs_t const & o, ulong desc_bound ) {
   HIPCHK( hipMemcpyAsync( s->d_toff,  s->h_toff,  4UL*c,        hipMemcpyHostToDevice, s->stream ) );
   HIPCHK( hipMemcpyAsync( s->d_tsz,   s->h_tsz,   4UL*c,        hipMemcpyHostToDevice, s->stream ) );
   HIPCHK( hipMemcpyAsync( s->d_tbase, s->h_tbase, 4UL*(c+1UL),  hipMemcpyHostToDevice, s->stream ) );
   if( blob_sz ) HIPCHK( hipMemcpyAsync( s->d_blob, s->h_blob, blob_sz, hipMemcpyHostToDevice, s->stream ) );
-  return slot_launch_txn_dev( s, c, nslot, t_out, s_out, tt_out, st_out, dq );
-}
-
-/* The kernels of a transaction chunk whose payloads and planes (d_blob,
-   d_toff, d_tsz, d_tbase[0..c]) are on the device, or on their way there on
-   the slot's stream: parse, verify with d_skip, reduce, outputs, tags,
-   descriptors. */
-static int
-slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, schar * t_out, schar * s_out, ulong * tt_out, ulong * st_out,
-                     desc_req_t const * dq ) {
-  if( fd_amd_launch_txn_parse( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, s->d_fp, NULL, 0, s->d_tbase,
-                               s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_skip, s->stream ) )
-    return FD_ED25519_AMD_ERR_DEVICE;
-  if( nslot && fd_amd_launch_verify( (uint32_t)nslot, s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_blob, s->d_err,
-                                     s->d_ws, s->stream, 0, NULL, s->d_skip, 0, NULL, s->strict ) )
-    return FD_ED25519_AMD_ERR_DEVICE;
-  /* after k_strict (same stream): a transaction's verdict is its first failing signature's code in the engine's mode */
-  if( fd_amd_launch_txn_reduce( (uint32_t)c, s->d_fp, s->d_tbase, s->d_err, s->d_terr, s->stream ) )
-    return FD_ED25519_AMD_ERR_DEVICE;
-  HIPCHK( slot_out( s, s->m_terr, s->d_terr, c ) );
-  if( s_out && nslot ) HIPCHK( slot_out( s, s->m_err, s->d_err, nslot ) );
-  /* tags: per transaction its first slot's (no slot launched: no workspace is read), per signature the plane */
-  if( tt_out && fd_amd_launch_tag_gather( s->m_ttag, s->d_ws, (uint32_t)c, s->d_tbase, s->stream ) ) return FD_ED25519_AMD_ERR_DEVICE;
-  if( st_out && nslot && slot_tags( s, nslot ) ) return FD_ED25519_AMD_ERR_DEVICE;
-  /* descriptors: packed in HBM from the footprints k_txn_parse left (0 where
-     it rejected the payload, the fail-closed slot mismatch included), then
-     one coalesced copy-out that reads the chunk's total on the device: the
-     host learns it from h_doff[c] when it drains the slot, without a sync */
-  if( dq ) {
-    if( fd_amd_launch_txn_pack( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, s->d_fp, s->d_dbsum, s->d_doff, s->d_desc,
-                                s->desc_stage, s->stream ) ||
-        fd_amd_launch_desc_out( s->m_desc, s->d_desc, s->m_doff, s->d_doff, (uint32_t)c, s->desc_stage, dq->bound, s->stream ) )
-      return FD_ED25519_AMD_ERR_DEVICE;
-  }
-  if( slot_done( s ) ) return FD_ED25519_AMD_ERR_DEVICE;
-  s->do_out = dq ? dq->off : NULL; s->do_n = c;
-  if( dq ) { s->d_out = dq->desc; s->d_cap = dq->cap; s->d_base = dq->base; }
-  s->tg_out = tt_out; s->tg_n = c;
-  s->g_out = nslot ? st_out : NULL; s->g_n = nslot;
-  s->t_out = t_out; s->t_n = c;
-  s->s_out = nslot ? s_out : NULL; s->s_n = nslot;
-  s->chk_err = (s_out && nslot) ? nslot : 0; s->chk_terr = c;
-  s->busy = 1;
-  return FD_ED25519_AMD_OK;
+  return slot_launch_txn_dev( s, c, nslot, o, desc_bound );
 }
 
 /* The chunk driver of every host batch call: `total` items (signatures or
@@ -677,14 +706,7 @@ slot_launch_dma( slot_t * s, ulong c, uchar const * pub, uchar const * sig, uint
   HIPCHK( hipMemcpyAsync( s->d_sz,  sz,  4UL*c,  hipMemcpyHostToDevice, s->stream ) );
   if( win ) HIPCHK( hipMemcpyAsync( s->d_blob, win_src, win, hipMemcpyHostToDevice, s->stream ) );
   if( fd_amd_launch_rebase_off( (uint32_t)c, s->d_off, s->d_sz, lo, s->stream ) ) return FD_ED25519_AMD_ERR_DEVICE;
-  if( fd_amd_launch_verify( (uint32_t)c, s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_blob, s->d_err, s->d_ws, s->stream,
-                            1, NULL, NULL, 0, NULL, s->strict ) )
-    return FD_ED25519_AMD_ERR_DEVICE;
-  HIPCHK( slot_out( s, s->m_err, s->d_err, c ) );
-  if( tag && slot_tags( s, c ) ) return FD_ED25519_AMD_ERR_DEVICE;
-  if( slot_done( s ) ) return FD_ED25519_AMD_ERR_DEVICE;
-  slot_in_flight( s, out, tag, c );
-  return FD_ED25519_AMD_OK;
+  return slot_launch_sig( s, c, slot_planes( s ), out, tag );
 }
 
 extern "C" int
@@ -710,19 +732,15 @@ fd_ed25519_amd_verify_soa_registered_tag( fd_ed25519_amd_t * e, ulong n, uchar c
   if( !(blob && blob_sz) ) d[4] = d[0];   /* no message bytes: any valid address */
   if( n <= e->cap && fd_amd_uses_latency_path( (uint32_t)n, 0 ) )
     /* a latency-path batch is read once, by k_front: it reads the caller's
-       registered planes in place over PCIe, with no copy on either side --
-       one chunk on a ring of one slot */
+       registered planes in place over PCIe, with no copy on either side (the
+       verdicts go out in place too: slot_launch_sig) -- one chunk on a ring
+       of one slot */
     return run_ring( e, 1, n, [&]( slot_t * s, ulong ) -> long {
       if( tag ) { int rc = slot_alloc_tag( s, e->cap ); if( rc ) return rc; }
-      /* the DSM kernel (strict mode: k_strict) writes the verdicts into the mapped h_err itself */
-      if( fd_amd_launch_verify( (uint32_t)n, (uint8_t const *)d[0], (uint8_t const *)d[1], (uint32_t const *)d[2],
-                                (uint32_t const *)d[3], (uint8_t const *)d[4], s->d_err, s->d_ws, s->stream, 1, NULL,
-                                NULL, 0, (int8_t *)s->m_err, s->strict ) )
-        return FD_ED25519_AMD_ERR_DEVICE;
-      if( tag && slot_tags( s, n ) ) return FD_ED25519_AMD_ERR_DEVICE;   /* k_tag_out after the DSM kernel, as slot_launch_packed */
-      if( hipEventRecord( s->done, s->stream ) != hipSuccess ) return FD_ED25519_AMD_ERR_DEVICE;
-      slot_in_flight( s, err, tag, n );
-      return (long)n;
+      planes_t const p = { (uint8_t const *)d[0], (uint8_t const *)d[1], (uint32_t const *)d[2], (uint32_t const *)d[3],
+                           (uint8_t const *)d[4] };
+      int rc = slot_launch_sig( s, n, p, err, tag );
+      return rc ? rc : (long)n;
     } );
   return run_ring( e, e->nslot, n, [&]( slot_t * s, ulong i ) -> long {
     if( tag ) { int rc = slot_alloc_tag( s, e->cap ); if( rc ) return rc; }
@@ -791,7 +809,7 @@ struct reg_view_t {
 }
 
 /* Chunk of c signatures whose records sit in s->h_pack: k_gather fetches
-   them into the slot's planes, then the pipeline of slot_launch_dma.  The
+   them into the slot's planes, then slot_launch_sig on those.  The
    records reach the kernel in place (it reads the mapped h_pack, 32 B per
    signature, once) or, with copy, by one H2D into d_pack. */
 static int
@@ -811,32 +829,17 @@ slot_launch_gather( slot_t * s, ulong c, bool copy, schar * out, ulong * tag ) {
      chunk with nothing beside it: no cap. */
   if( fd_amd_launch_gather( (uint32_t)c, d_rec, s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_blob, lat ? 0u : 64u, s->stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
-  if( fd_amd_launch_verify( (uint32_t)c, s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_blob, s->d_err, s->d_ws, s->stream,
-                            1, NULL, NULL, 0, lat ? (int8_t *)s->m_err : NULL, s->strict ) )
-    return FD_ED25519_AMD_ERR_DEVICE;
-  if( !lat ) HIPCHK( slot_out( s, s->m_err, s->d_err, c ) );
-  if( tag && slot_tags( s, c ) ) return FD_ED25519_AMD_ERR_DEVICE;
-  if( slot_done( s ) ) return FD_ED25519_AMD_ERR_DEVICE;
-  slot_in_flight( s, out, tag, c );
-  return FD_ED25519_AMD_OK;
+  return slot_launch_sig( s, c, slot_planes( s ), out, tag );
 }
 
-/* Every signature of a registered pointer-array batch, before anything
-   launches: its pointers, its size, and the first and last byte of each
-   range in one registration of the table.  True when all pass. */
+/* check( lo, hi ) over [0, n), true when it holds on every part.  The
+   registered calls' up-front pass reads a pointer, a size and at most one
+   payload byte per item and nothing of it overlaps the GPU: large batches
+   (2^18 items and up) split it over up to 4 host threads, as copy_par does
+   the staging copies. */
+template<typename CHECK>
 static bool
-batch_registered_check( fd_ed25519_amd_t const * e, reg_view_t const & view, ulong n, void const * const * msg,
-                        ulong const * sz, void const * const * sig, void const * const * pub ) {
-  auto check = [&]( ulong lo, ulong hi ) -> bool {
-    reg_view_t v = view;                     /* its own last-hit index */
-    fd_amd_gather_rec_t probe;
-    for( ulong j=lo; j<hi; j++ )
-      if( sz[j] > e->blob_cap || !v.rec( &probe, pub[j], sig[j], msg[j], sz[j] ) ) return false;
-    return true;
-  };
-  /* the pass reads 32 B of pointers and sizes per signature and nothing of
-     it overlaps the GPU: large batches split it over up to 4 host threads,
-     as copy_par does the staging copies */
+check_par( ulong n, CHECK check ) {
   int nt = (int)( n >> 17 ); if( nt > 4 ) nt = 4;
   if( nt < 2 ) return check( 0UL, n );
   std::thread th[3]; bool ok[4];
@@ -846,6 +849,22 @@ batch_registered_check( fd_ed25519_amd_t const * e, reg_view_t const & view, ulo
   for( int t=1; t<nt; t++ ) th[t-1].join();
   for( int t=0; t<nt; t++ ) if( !ok[t] ) return false;
   return true;
+}
+
+/* Every signature of a registered pointer-array batch, before anything
+   launches: its pointers, its size, and the first and last byte of each
+   range in one registration of the table (32 B of pointers and sizes read
+   per signature).  True when all pass. */
+static bool
+batch_registered_check( fd_ed25519_amd_t const * e, reg_view_t const & view, ulong n, void const * const * msg,
+                        ulong const * sz, void const * const * sig, void const * const * pub ) {
+  return check_par( n, [&]( ulong lo, ulong hi ) -> bool {
+    reg_view_t v = view;                     /* its own last-hit index */
+    fd_amd_gather_rec_t probe;
+    for( ulong j=lo; j<hi; j++ )
+      if( sz[j] > e->blob_cap || !v.rec( &probe, pub[j], sig[j], msg[j], sz[j] ) ) return false;
+    return true;
+  } );
 }
 
 /* Where a slot keeps a gathered chunk's dst offsets: behind its records in
@@ -905,20 +924,6 @@ fd_amd_txn_slots1( uchar const * p, ulong sz ) {
   return ( k >= 1UL && k <= FD_TXN_SIG_MAX && 64UL*k <= sz - 1UL ) ? k : 0UL;
 }
 
-int
-fd_amd_txn_args_check( fd_ed25519_amd_t const * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
-                       uint const * txn_sz, ulong payload_sz, schar const * txn_err, uint const * sig_base,
-                       schar const * sig_err, ulong const * sig_tag ) {
-  if( !e || (txn_cnt && (!payload || !txn_off || !txn_sz || !txn_err)) ) return FD_ED25519_AMD_ERR_INVAL;
-  if( (sig_err || sig_tag) && !sig_base ) return FD_ED25519_AMD_ERR_INVAL;
-  for( ulong t=0; t<txn_cnt; t++ ) {
-    if( txn_sz[t] > FD_TXN_AMD_MTU || (ulong)txn_off[t] + txn_sz[t] > payload_sz || txn_sz[t] > e->blob_cap )
-      return FD_ED25519_AMD_ERR_INVAL;
-    if( fd_amd_txn_slots1( payload + txn_off[t], txn_sz[t] ) > e->cap ) return FD_ED25519_AMD_ERR_INVAL;
-  }
-  return FD_ED25519_AMD_OK;
-}
-
 extern "C" int
 fd_ed25519_amd_verify_txns( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
                             uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err ) {
@@ -950,15 +955,6 @@ fd_txn_amd_desc_bound( ulong payload_sz ) {
   return ( payload_sz <= FD_TXN_AMD_MTU && b > FD_TXN_MAX_SZ ) ? FD_TXN_MAX_SZ : b;
 }
 
-/* Where one transaction chunk's outputs go: the caller's arrays at the
-   chunk's first transaction (txn_err, txn_tag, desc_off) and first signature
-   slot (sig_err, sig_tag), NULL where not asked for; the whole descriptor
-   buffer, and the call's running descriptor byte base. */
-struct txn_outs_t {
-  schar * txn_err; schar * sig_err; ulong * txn_tag; ulong * sig_tag;
-  ulong * desc_off; uchar * desc; ulong desc_cap; ulong * dbase;
-};
-
 /* The first buffers a transaction chunk needs on its slot. */
 static int
 slot_alloc_txn( fd_ed25519_amd_t const * e, slot_t * s, txn_outs_t const & o ) {
@@ -968,14 +964,16 @@ slot_alloc_txn( fd_ed25519_amd_t const * e, slot_t * s, txn_outs_t const & o ) {
   return rc;
 }
 
-/* The argument check of the staged transaction calls (the descriptor
-   capacity is decided by the bound, never by the data). */
+/* The output-argument check of every transaction call, staged (SZ = uint)
+   or registered (SZ = ulong): sig_base given whenever a per-signature output
+   (sig_err, sig_tag) is; desc and desc_off both or neither; and desc_cap at
+   least the sum of fd_txn_amd_desc_bound (the descriptor capacity is decided
+   by the bound, never by the data).  txn_sz: not NULL when txn_cnt > 0. */
+template<typename SZ>
 static int
-txns_args_check( fd_ed25519_amd_t const * e, ulong txn_cnt, uchar const * payload, uint const * txn_off, uint const * txn_sz,
-                 ulong payload_sz, schar const * txn_err, uint const * sig_base, schar const * sig_err, ulong const * sig_tag,
-                 ulong const * desc_off, uchar const * desc, ulong desc_cap ) {
-  int rc = fd_amd_txn_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag );
-  if( rc ) return rc;
+txn_outs_check( ulong txn_cnt, SZ const * txn_sz, uint const * sig_base, schar const * sig_err, ulong const * sig_tag,
+                ulong const * desc_off, uchar const * desc, ulong desc_cap ) {
+  if( (sig_err || sig_tag) && !sig_base ) return FD_ED25519_AMD_ERR_INVAL;
   if( !desc != !desc_off ) return FD_ED25519_AMD_ERR_INVAL;
   if( desc_off ) {
     ulong need = 0;
@@ -985,17 +983,43 @@ txns_args_check( fd_ed25519_amd_t const * e, ulong txn_cnt, uchar const * payloa
   return FD_ED25519_AMD_OK;
 }
 
-/* The chunk the staged transaction call cuts off the front of txn_cnt
-   transactions: bounded by their count, their signature slots and their
-   bytes. */
+int
+fd_amd_txn_args_check( fd_ed25519_amd_t const * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
+                       uint const * txn_sz, ulong payload_sz, schar const * txn_err, uint const * sig_base,
+                       schar const * sig_err, ulong const * sig_tag, ulong const * desc_off, uchar const * desc,
+                       ulong desc_cap ) {
+  if( !e || (txn_cnt && (!payload || !txn_off || !txn_sz || !txn_err)) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( txn_outs_check( txn_cnt, txn_sz, sig_base, sig_err, sig_tag, desc_off, desc, desc_cap ) ) return FD_ED25519_AMD_ERR_INVAL;
+  for( ulong t=0; t<txn_cnt; t++ ) {
+    if( txn_sz[t] > FD_TXN_AMD_MTU || (ulong)txn_off[t] + txn_sz[t] > payload_sz || txn_sz[t] > e->blob_cap )
+      return FD_ED25519_AMD_ERR_INVAL;
+    if( fd_amd_txn_slots1( payload + txn_off[t], txn_sz[t] ) > e->cap ) return FD_ED25519_AMD_ERR_INVAL;
+  }
+  return FD_ED25519_AMD_OK;
+}
+
+/* The chunk rule of the staged transaction calls, stated once: the chunk cut
+   off the front of txn_cnt transactions is bounded by their count, their
+   signature slots and their bytes.  take( j, p, sz, bsz, ns ) is called for
+   every transaction j the chunk takes: its payload p of sz bytes, and the
+   bytes and signature slots of the chunk before it.  A payload's first
+   byte, which gives its slots, is read from caller memory once per decision:
+   the read that bounds the chunk (ns <= cap is what keeps the slot's planes
+   in bounds) is the one whose running sum `take` stages.  Returns the
+   transactions taken, their bytes in *bytes and their slots in *slots. */
+template<typename TAKE>
 static ulong
-txns_chunk( fd_ed25519_amd_t const * e, ulong txn_cnt, uchar const * payload, uint const * txn_off, uint const * txn_sz ) {
+txns_chunk( fd_ed25519_amd_t const * e, ulong txn_cnt, uchar const * payload, uint const * txn_off, uint const * txn_sz,
+            ulong * bytes, ulong * slots, TAKE take ) {
   ulong c = 0, bsz = 0, ns = 0;
   while( c < txn_cnt && c < e->cap ) {
-    ulong sz = txn_sz[c], k2 = fd_amd_txn_slots1( payload + txn_off[c], sz );
+    uchar const * p = payload + txn_off[c];
+    ulong sz = txn_sz[c], k2 = fd_amd_txn_slots1( p, sz );
     if( bsz + sz > e->blob_cap || ns + k2 > e->cap ) break;
+    take( c, p, sz, bsz, ns );
     bsz += sz; ns += k2; c++;
   }
+  *bytes = bsz; *slots = ns;
   return c;
 }
 
@@ -1008,20 +1032,15 @@ stage_txns( fd_ed25519_amd_t * e, slot_t * s, ulong txn_cnt, uchar const * paylo
             uint const * txn_sz, txn_outs_t const & o, ulong * slots ) {
   int rc = slot_alloc_txn( e, s, o );
   if( rc ) return rc;
-  ulong c = 0, bsz = 0, ns = 0;
-  desc_req_t dq = { o.desc_off, o.desc, o.desc_cap, o.dbase, 0UL };
-  while( c < txn_cnt && c < e->cap ) {
-    uchar const * p = payload + txn_off[c];
-    ulong sz = txn_sz[c], k2 = fd_amd_txn_slots1( p, sz );
-    if( bsz + sz > e->blob_cap || ns + k2 > e->cap ) break;   /* txns_chunk's rule */
-    if( sz ) memcpy( s->h_blob + bsz, p, sz );
-    s->h_toff[c] = (uint32_t)bsz; s->h_tsz[c] = (uint32_t)sz; s->h_tbase[c] = (uint32_t)ns;
-    if( o.desc_off ) dq.bound += fd_txn_amd_desc_bound( sz );
-    bsz += sz; ns += k2; c++;
-  }
-  s->h_tbase[c] = (uint32_t)ns;
-  rc = slot_launch_txn( s, c, ns, bsz, o.txn_err, o.sig_err, o.txn_tag, o.sig_tag, o.desc_off ? &dq : NULL );
-  *slots = ns;
+  ulong bsz = 0, bound = 0;
+  ulong const c = txns_chunk( e, txn_cnt, payload, txn_off, txn_sz, &bsz, slots,
+                              [&]( ulong j, uchar const * p, ulong sz, ulong b, ulong ns ) {
+    if( sz ) memcpy( s->h_blob + b, p, sz );
+    s->h_toff[j] = (uint32_t)b; s->h_tsz[j] = (uint32_t)sz; s->h_tbase[j] = (uint32_t)ns;
+    if( o.desc_off ) bound += fd_txn_amd_desc_bound( sz );
+  } );
+  s->h_tbase[c] = (uint32_t)*slots;
+  rc = slot_launch_txn( s, c, *slots, bsz, o, bound );
   return rc ? rc : (long)c;
 }
 
@@ -1030,8 +1049,8 @@ fd_ed25519_amd_verify_txns_desc( fd_ed25519_amd_t * e, ulong txn_cnt, uchar cons
                                  uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                                  ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap ) {
   if( SYNC_REFUSED( e ) ) return FD_ED25519_AMD_ERR_INVAL;
-  int rc = txns_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag,
-                            desc_off, desc, desc_cap );
+  int rc = fd_amd_txn_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag,
+                                  desc_off, desc, desc_cap );
   if( rc ) return rc;
   if( desc_off ) desc_off[0] = 0UL;
   ulong dbase = 0;   /* descriptor bytes of the chunks delivered so far */
@@ -1088,8 +1107,7 @@ fd_ed25519_amd_txn_gather_layout( ulong n, ulong const * sz, uint const * slots,
    place (it reads the mapped h_pack, 32 B per transaction, once), as
    slot_launch_gather's do. */
 static int
-slot_launch_txn_gather( slot_t * s, ulong c, ulong nslot, uint waves, schar * t_out, schar * s_out, ulong * tt_out,
-                        ulong * st_out, desc_req_t const * dq ) {
+slot_launch_txn_gather( slot_t * s, ulong c, ulong nslot, uint waves, txn_outs_t const & o, ulong desc_bound ) {
   /* A throughput chunk's gather runs beside the other slots' verify kernels
      and its reads of host memory hold up their memory traffic
      (slot_launch_gather): capped at `waves` waves, 64 unless
@@ -1100,7 +1118,7 @@ slot_launch_txn_gather( slot_t * s, ulong c, ulong nslot, uint waves, schar * t_
   if( fd_amd_launch_gather_txn( (uint32_t)c, (fd_amd_gather_txn_rec_t const *)s->m_pack, s->d_blob, s->d_toff, s->d_tsz,
                                 s->d_tbase, (uint32_t)nslot, lat ? 0u : waves, s->stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
-  return slot_launch_txn_dev( s, c, nslot, t_out, s_out, tt_out, st_out, dq );
+  return slot_launch_txn_dev( s, c, nslot, o, desc_bound );
 }
 
 extern "C" int
@@ -1117,25 +1135,20 @@ fd_ed25519_amd_verify_txns_registered_tag( fd_ed25519_amd_t * e, ulong txn_cnt, 
                                                      NULL, NULL, 0UL );
 }
 
-/* The argument check of the registered transaction calls, for
-   txn_cnt > 0.  Every transaction before anything launches: its pointer, its
-   size, its first and last byte in one registration of the table, and the
-   signature slots it reserves -- read here, once, from payload[0] into
-   slots[0 .. txn_cnt): the chunks and sig_base use this count, whatever the
-   byte holds later. */
+/* The argument check of the registered transaction calls, after e and the
+   count: the arrays and the outputs (txn_outs_check), then every transaction
+   before anything launches: its pointer, its size, its first and last byte
+   in one registration of the table (16 B of pointer and size read per
+   transaction), and the signature slots it reserves -- read here, once,
+   from payload[0] into slots[0 .. txn_cnt): the chunks and sig_base use this
+   count, whatever the byte holds later. */
 static int
 txns_registered_check( fd_ed25519_amd_t const * e, reg_view_t const & view, ulong txn_cnt, void const * const * txn,
                        ulong const * txn_sz, schar const * txn_err, uint const * sig_base, schar const * sig_err,
                        ulong const * sig_tag, ulong const * desc_off, uchar const * desc, ulong desc_cap, uint * slots ) {
-  if( !txn || !txn_sz || !txn_err ) return FD_ED25519_AMD_ERR_INVAL;
-  if( (sig_err || sig_tag) && !sig_base ) return FD_ED25519_AMD_ERR_INVAL;
-  if( !desc != !desc_off ) return FD_ED25519_AMD_ERR_INVAL;
-  if( desc_off ) {   /* capacity is decided by the bound, never by the data */
-    ulong need = 0;
-    for( ulong t=0; t<txn_cnt; t++ ) need += fd_txn_amd_desc_bound( txn_sz[t] );
-    if( desc_cap < need ) return FD_ED25519_AMD_ERR_INVAL;
-  }
-  auto check = [&]( ulong lo, ulong hi ) -> bool {
+  if( txn_cnt && (!txn || !txn_sz || !txn_err) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( txn_outs_check( txn_cnt, txn_sz, sig_base, sig_err, sig_tag, desc_off, desc, desc_cap ) ) return FD_ED25519_AMD_ERR_INVAL;
+  bool const ok = check_par( txn_cnt, [&]( ulong lo, ulong hi ) -> bool {
     reg_view_t v = view;                     /* its own last-hit index */
     for( ulong t=lo; t<hi; t++ ) {
       ulong const sz = txn_sz[t];
@@ -1147,21 +1160,8 @@ txns_registered_check( fd_ed25519_amd_t const * e, reg_view_t const & view, ulon
       slots[t] = (uint)k;
     }
     return true;
-  };
-  /* the pass reads 16 B of pointer and size and one payload byte per
-     transaction and nothing of it overlaps the GPU: large batches split it
-     over up to 4 host threads, as fd_ed25519_amd_verify_batch_registered */
-  int nt = (int)( txn_cnt >> 17 ); if( nt > 4 ) nt = 4;
-  if( nt < 2 ) { if( !check( 0UL, txn_cnt ) ) return FD_ED25519_AMD_ERR_INVAL; }
-  else {
-    std::thread th[3]; bool ok[4];
-    ulong const part = ( txn_cnt + (ulong)nt - 1UL ) / (ulong)nt;
-    for( int t=1; t<nt; t++ ) th[t-1] = std::thread( [&, t]{ ok[t] = check( part*(ulong)t, std::min( txn_cnt, part*(ulong)(t+1) ) ); } );
-    ok[0] = check( 0UL, part );
-    for( int t=1; t<nt; t++ ) th[t-1].join();
-    for( int t=0; t<nt; t++ ) if( !ok[t] ) return FD_ED25519_AMD_ERR_INVAL;
-  }
-  return FD_ED25519_AMD_OK;
+  } );
+  return ok ? FD_ED25519_AMD_OK : FD_ED25519_AMD_ERR_INVAL;
 }
 
 /* The caller-visible global signature numbering from the checked counts. */
@@ -1181,13 +1181,12 @@ stage_txns_registered( fd_ed25519_amd_t * e, slot_t * s, reg_view_t & view, ulon
                        ulong const * txn_sz, uint const * slots, txn_outs_t const & o, ulong * slot_cnt ) {
   int rc = slot_alloc_txn( e, s, o );
   if( rc ) return rc;
-  desc_req_t dq = { o.desc_off, o.desc, o.desc_cap, o.dbase, 0UL };
   /* the chunk's records in h_pack (32 B per transaction), their dst behind them */
   fd_amd_gather_txn_rec_t * rec = (fd_amd_gather_txn_rec_t *)s->h_pack;
   uint * dst = slot_gather_dst( e, s );
   ulong ns = 0;
   ulong c = fd_ed25519_amd_txn_gather_layout( txn_cnt, txn_sz, slots, e->cap, e->blob_cap, dst, &ns );
-  ulong b = 0;
+  ulong b = 0, bound = 0;
   for( ulong j=0; j<c; j++ ) {
     /* translated again, not kept from the check (fd_ed25519_amd_verify_batch_registered):
        an address the table does not give never reaches the kernel */
@@ -1196,11 +1195,10 @@ stage_txns_registered( fd_ed25519_amd_t * e, slot_t * s, reg_view_t & view, ulon
     if( sz > FD_TXN_AMD_MTU || sz > e->blob_cap || ( sz && ( !txn[j] || !view.xlat( txn[j], sz, &rec[j].src ) ) ) )
       return FD_ED25519_AMD_ERR_INVAL;
     rec[j].sz = (uint32_t)sz; rec[j].dst = dst[j]; rec[j].tbase = (uint32_t)b;
-    if( o.desc_off ) dq.bound += fd_txn_amd_desc_bound( sz );
+    if( o.desc_off ) bound += fd_txn_amd_desc_bound( sz );
     b += slots[j];
   }
-  rc = slot_launch_txn_gather( s, c, ns, (uint)e->gather_txn_waves, o.txn_err, o.sig_err, o.txn_tag, o.sig_tag,
-                               o.desc_off ? &dq : NULL );
+  rc = slot_launch_txn_gather( s, c, ns, (uint)e->gather_txn_waves, o, bound );
   *slot_cnt = ns;
   return rc ? rc : (long)c;
 }
@@ -1210,12 +1208,7 @@ fd_ed25519_amd_verify_txns_registered_desc( fd_ed25519_amd_t * e, ulong txn_cnt,
                                             ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                                             ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc,
                                             ulong desc_cap ) {
-  if( SYNC_REFUSED( e ) ) return FD_ED25519_AMD_ERR_INVAL;
-  if( !e || (txn_cnt && (!txn || !txn_sz || !txn_err)) ) return FD_ED25519_AMD_ERR_INVAL;
-  if( (sig_err || sig_tag) && !sig_base ) return FD_ED25519_AMD_ERR_INVAL;
-  if( !desc != !desc_off ) return FD_ED25519_AMD_ERR_INVAL;
-  if( txn_cnt > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
-  if( !txn_cnt ) { if( sig_base ) sig_base[0] = 0U; if( desc_off ) desc_off[0] = 0UL; return FD_ED25519_AMD_OK; }
+  if( SYNC_REFUSED( e ) || !e || txn_cnt > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
   reg_view_t view;
   std::vector<uint> slots( txn_cnt );
   int rc = txns_registered_check( e, view, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, sig_tag, desc_off, desc,
@@ -1223,6 +1216,7 @@ fd_ed25519_amd_verify_txns_registered_desc( fd_ed25519_amd_t * e, ulong txn_cnt,
   if( rc ) return rc;
   if( desc_off ) desc_off[0] = 0UL;
   if( sig_base ) txns_sig_base( txn_cnt, slots.data(), sig_base );
+  if( !txn_cnt ) return FD_ED25519_AMD_OK;   /* before anything touches the device */
   ulong gsig = 0;
   ulong dbase = 0;   /* descriptor bytes of the chunks delivered so far */
   return run_ring( e, e->nslot, txn_cnt, [&]( slot_t * s, ulong t ) -> long {
@@ -1474,15 +1468,16 @@ fd_ed25519_amd_submit_txns( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * p
                             ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
                             ulong * ticket ) {
   if( !e || !ticket || !txn_cnt ) return FD_ED25519_AMD_ERR_INVAL;
-  int rc = txns_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag,
-                            desc_off, desc, desc_cap );
+  int rc = fd_amd_txn_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag,
+                                  desc_off, desc, desc_cap );
   if( rc ) return rc;
   slot_t * s = submit_slot( e, &rc );
   if( !s ) return rc;
-  if( txns_chunk( e, txn_cnt, payload, txn_off, txn_sz ) != txn_cnt ) return FD_ED25519_AMD_ERR_INVAL;   /* one chunk */
+  ulong bsz = 0, ns = 0;
+  if( txns_chunk( e, txn_cnt, payload, txn_off, txn_sz, &bsz, &ns, []( ulong, uchar const *, ulong, ulong, ulong ){} ) != txn_cnt )
+    return FD_ED25519_AMD_ERR_INVAL;   /* one chunk */
   s->a_dbase = 0UL;
   txn_outs_t o = { txn_err, sig_err, txn_tag, sig_tag, desc_off, desc, desc_cap, &s->a_dbase };
-  ulong ns = 0;
   rc = submit_run( e, s, ticket, [&]() -> long { return stage_txns( e, s, txn_cnt, payload, txn_off, txn_sz, o, &ns ); } );
   /* pure host numbering: the one output a submit call writes */
   if( !rc && sig_base ) fd_ed25519_amd_txn_slots( txn_cnt, payload, txn_off, txn_sz, sig_base );

@@ -11,6 +11,25 @@
 #include <stdint.h>
 #include "../../include/fd_ed25519_amd.h"
 
+/* The chunk in flight on a slot: what slot_drain delivers to the caller once
+   the slot's event has fired, written by the two launch tails
+   (slot_launch_sig, slot_launch_txn_dev) and cleared by slot_forget alone. */
+struct slot_flight_t {
+  /* verdicts and tags: the first ncp of cp[], each `sz` bytes from the slot's
+     mapped staging (h_err, h_terr, h_tag, h_ttag) to the caller's array */
+  struct { void * dst; void const * src; ulong sz; } cp[4];
+  int     ncp;
+  ulong   chk_err, chk_terr;   /* verdict bytes the launch writes to h_err / h_terr (checked for FD_AMD_VERDICT_DEVICE) */
+  /* descriptors (do_out NULL: not asked for): on delivery
+     do_out[0 .. do_n] = *d_base + h_doff[..] (do_n: the chunk's transactions),
+     the h_doff[do_n] bytes go to d_out + *d_base (d_cap: the caller's
+     capacity) and *d_base grows by them -- so chunks must be drained in the
+     order they were launched */
+  ulong * do_out; ulong do_n;
+  uchar * d_out;  ulong d_cap;
+  ulong * d_base;
+};
+
 struct slot_t {
   /* device */
   uint8_t  * d_pub;  uint8_t * d_sig; uint8_t * d_blob;
@@ -23,30 +42,19 @@ struct slot_t {
   uint8_t  * m_pack;                     /* device address of the mapped h_pack (latency path reads it in place) */
   void * m_err, * m_terr;   /* device addresses of the mapped h_err / h_terr */
   int        strict;     /* the owning engine's mode (fd_ed25519_amd_set_mode): 1 = its launches add k_strict */
-  /* the chunk in flight: where its verdicts go */
-  schar *    out;
-  ulong      n;
-  int        busy;
-  ulong      chk_err, chk_terr;   /* verdict bytes the launch writes to h_err / h_terr (checked for FD_AMD_VERDICT_DEVICE) */
+  int        busy;       /* a chunk is in flight: `fl` says where its outputs go */
+  slot_flight_t fl;
   /* transaction front end (allocated on first use): per-transaction
      payload offset/size, footprint, signature-slot base, verdict; per-slot
      skip plane */
   uint32_t * d_toff; uint32_t * d_tsz; uint32_t * d_fp; uint32_t * d_tbase; int8_t * d_terr; int8_t * d_skip;
   uint32_t * h_toff; uint32_t * h_tsz; uint32_t * h_tbase; int8_t * h_terr;
-  /* transaction chunk in flight */
-  schar *    t_out;      /* per-transaction verdicts */
-  ulong      t_n;
-  schar *    s_out;      /* per-signature verdicts (optional) */
-  ulong      s_n;
   /* dedup tags (allocated by the first call that asks for them): one mapped
      pinned buffer, h_tag[cap] for per-signature tags and h_ttag[cap] behind
      it for per-transaction tags, both written in place by k_tag_out /
      k_tag_gather; m_tag / m_ttag: their device addresses */
   ulong * h_tag;  ulong * h_ttag;
   void  * m_tag;  void  * m_ttag;
-  /* tags of the chunk in flight (NULL: not asked for): g_n from h_tag, tg_n from h_ttag */
-  ulong * g_out;  ulong g_n;
-  ulong * tg_out; ulong tg_n;
   /* packed descriptors (allocated by the first call that asks for them).
      d_dpack, one device allocation: d_doff[cap+1], the chunk-relative 64-bit
      offsets; d_dbsum, the scan's block totals; d_desc[desc_stage], the packed
@@ -57,32 +65,17 @@ struct slot_t {
   uint8_t * h_dpack; ulong * h_doff; uint8_t * h_desc;
   void    * m_doff;  void  * m_desc;
   ulong     desc_stage;
-  /* descriptors of the chunk in flight (do_out NULL: not asked for): on
-     delivery do_out[0 .. do_n] = *d_base + h_doff[..], the h_doff[do_n] bytes
-     go to d_out + *d_base (d_cap: the caller's capacity) and *d_base grows
-     by them -- so chunks must be drained in the order they were launched */
-  ulong * do_out; ulong do_n;
-  uchar * d_out;  ulong d_cap;
-  ulong * d_base;
   /* asynchronous submissions (fd_ed25519_amd_submit_*): the ticket the slot
      carries; its completion word, 8 bytes on a 64-byte line of their own in
      mapped coherent pinned memory, to which k_ticket stores that ticket behind
      the chunk's kernels (m_tick: its device address); tick_arm: the launch
      under way is a submission that polls the word, so the slot's launch ends
      with k_ticket; a_dbase: the descriptor byte base of a submission (always 0:
-     it is one chunk), what d_base points at */
+     it is one chunk), what fl.d_base points at */
   ulong   ticket;
   ulong * h_tick; void * m_tick;
   int     tick_arm;
   ulong   a_dbase;
-};
-
-/* What a transaction chunk's launch needs to return descriptors: where the
-   chunk's offsets go (its first transaction's entry of the caller's
-   desc_off), the caller's buffer and capacity, the call's running byte base,
-   and the chunk's bound (the sum of fd_txn_amd_desc_bound over it). */
-struct desc_req_t {
-  ulong * off; uchar * desc; ulong cap; ulong * base; ulong bound;
 };
 
 #define FD_AMD_SLOT_MAX (FD_ED25519_AMD_SLOT_MAX)
@@ -128,12 +121,14 @@ fd_amd_mode_ok( int mode ) {
    chunk loop always makes progress.  SoA: every message in bounds and small
    enough for one chunk.  Transactions: each in bounds and stageable in one
    chunk (its bytes in blob_max, its signatures in batch_max); sig_base given
-   whenever a per-signature output (sig_err, sig_tag) is. */
+   whenever a per-signature output (sig_err, sig_tag) is; desc and desc_off
+   both or neither, with room for the sum of fd_txn_amd_desc_bound. */
 int fd_amd_soa_args_check( fd_ed25519_amd_t const * e, ulong n, uchar const * pub, uchar const * sig, uint const * msg_off,
                            uint const * msg_sz, uchar const * blob, ulong blob_sz, schar const * err );
 int fd_amd_txn_args_check( fd_ed25519_amd_t const * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
                            uint const * txn_sz, ulong payload_sz, schar const * txn_err, uint const * sig_base,
-                           schar const * sig_err, ulong const * sig_tag );
+                           schar const * sig_err, ulong const * sig_tag, ulong const * desc_off = NULL,
+                           uchar const * desc = NULL, ulong desc_cap = 0UL );
 
 /* signature slots reserved for a payload (fd_txn_parse.c:79-82 rule) */
 ulong fd_amd_txn_slots1( uchar const * p, ulong sz );

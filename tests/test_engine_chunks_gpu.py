@@ -262,9 +262,17 @@ def test_strict_mode_chunks(short):
     want = np.array(_strict_ref.verify_batch(b), np.int8)
     assert len(set(want.tolist())) >= 3
     e = ed25519.Engine(device=0, batch_max=CAP, blob_max=BLOB, mode=ed25519.MODE_STRICT)
+    r = ed25519.RegisteredPlanes(b.pub, b.sig, b.msg_off, b.msg_sz, b.blob)
     try:
         out = _three(e, b)
+        # the registered call's DMA chunks again with tags asked for: three of 64 and a last one of 8
+        terr, tag = e.verify_soa_registered(r[0], r[1], r[2], r[3], r[4], want_tags=True)
     finally:
+        r.close()
         e.close()
     del out["batch"]
     _check(out, want)
+    from test_tags_gpu import _expected as _tags
+    assert len(b) % CAP == 8
+    assert np.array_equal(terr, want), np.nonzero(terr != want)[0][:10]
+    assert np.array_equal(tag, _tags(b, exp)), np.nonzero(tag != _tags(b, exp))[0][:10]
