@@ -20,7 +20,9 @@
 #include <mutex>
 #include <vector>
 #include <pthread.h>
+#include <sys/random.h>
 #include <sys/syscall.h>
+#include <time.h>
 #include <unistd.h>
 #include <thread>
 
@@ -70,6 +72,8 @@ slot_free( slot_t * s ) {
   if( s->h_tag  ) (void)hipHostFree( s->h_tag );
   if( s->d_dpack) (void)hipFree( s->d_dpack );
   if( s->h_dpack) (void)hipHostFree( s->h_dpack );
+  if( s->d_kpack) (void)hipFree( s->d_kpack );
+  if( s->h_kpack) (void)hipHostFree( s->h_kpack );
   if( s->stream ) (void)hipStreamDestroy( s->stream );
   if( s->done   ) (void)hipEventDestroy( s->done );
   memset( s, 0, sizeof(*s) );
@@ -159,6 +163,13 @@ fd_ed25519_amd_new_slots( int device, ulong batch_max, ulong blob_max, ulong slo
   if( bad ) { fd_ed25519_amd_delete( e ); return NULL; }
   ev = getenv( "FD_ED25519_AMD_ASYNC_POLL" );
   e->poll_event = ev && !strcmp( ev, "event" );
+  /* the survivor filter's salt: a secret of this engine, from the OS; the
+     clock only where that fails (slot_alloc cleared the slots: set it last) */
+  if( getrandom( &e->salt, sizeof(e->salt), 0 ) != (ssize_t)sizeof(e->salt) ) {
+    struct timespec ts; (void)clock_gettime( CLOCK_MONOTONIC, &ts );
+    e->salt = ( (ulong)ts.tv_sec * 1000000007UL ) ^ ( (ulong)ts.tv_nsec << 21 ) ^ (ulong)(uintptr_t)e;
+  }
+  for( int k=0; k<nslot; k++ ) e->slot[k].salt = e->salt;
   return e;
 }
 
@@ -227,6 +238,32 @@ slot_alloc_desc( slot_t * s, ulong cap, ulong blob_cap ) {
   return FD_ED25519_AMD_OK;
 }
 
+/* The slot's survivor buffers, on the first submission that asks for the
+   publish list. */
+static int
+slot_alloc_keep( slot_t * s, ulong cap ) {
+  if( s->d_kpack ) return FD_ED25519_AMD_OK;
+  ulong const scr = fd_amd_keep_layout( cap ).total, pl = ( 8UL*cap + 255UL ) & ~255UL;   /* scr: a multiple of 256 */
+  HIPCHK( hipMalloc( (void **)&s->d_kpack, scr + 2UL*pl ) );
+  s->d_kscr = s->d_kpack; s->d_ktag = (ulong *)(s->d_kpack + scr); s->d_fpk = (uint32_t *)(s->d_kpack + scr + pl);
+  HIPCHK( hipHostMalloc( (void **)&s->h_kpack, 256UL + 4UL*cap, hipHostMallocMapped | hipHostMallocCoherent ) );
+  s->h_kcnt = (ulong *)s->h_kpack; s->h_keep = (uint *)(s->h_kpack + 256UL);
+  HIPCHK( hipHostGetDevicePointer( &s->m_kcnt, s->h_kpack, 0 ) );
+  s->m_keep = (uint8_t *)s->m_kcnt + 256UL;
+  return FD_ED25519_AMD_OK;
+}
+
+/* The filter step of both launch tails, for a _keep submission: the
+   survivors of the chunk's n items, from their verdicts d_err (in the
+   engine's mode: behind k_strict) and tags d_tag, both on the device, into
+   the mapped h_keep / h_kcnt -- written in place by the filter's last
+   kernels, as the verdicts are by slot_out.  fp / fpk: fd_amd_launch_keep's. */
+static int
+slot_keep( slot_t * s, ulong n, int8_t const * d_err, ulong const * d_tag, uint32_t const * fp, uint32_t * fpk ) {
+  return fd_amd_launch_keep( (uint32_t)n, d_err, (uint64_t const *)d_tag, fp, fpk, (uint32_t *)s->m_keep, (uint64_t *)s->m_kcnt,
+                             s->d_kscr, s->salt, s->stream ) ? FD_ED25519_AMD_ERR_DEVICE : FD_ED25519_AMD_OK;
+}
+
 /* The n tags of the chunk just verified on s (the tag plane of its
    workspace) into h_tag, on the slot's stream: k_tag_out writes the mapped
    buffer, on every path, as slot_out does the verdicts and for its reason.
@@ -265,8 +302,16 @@ slot_drain( slot_t * s ) {
   else if( f.do_out && ( s->h_doff[f.do_n] > s->desc_stage || *f.d_base + s->h_doff[f.do_n] > f.d_cap ) ) {
     fprintf( stderr, "fd_ed25519_amd: a chunk's descriptors exceed their bound\n" );
     fault = true;
+  } else if( f.k_out && s->h_kcnt[0] > f.k_n ) {   /* the same backstop for the publish list */
+    fprintf( stderr, "fd_ed25519_amd: a chunk's survivors exceed its items\n" );
+    fault = true;
   } else {
     for( int k=0; k<f.ncp; k++ ) memcpy( f.cp[k].dst, f.cp[k].src, f.cp[k].sz );
+    if( f.k_out ) {   /* keep[0, count) and the count; nothing at or beyond keep[count] */
+      ulong const cnt = s->h_kcnt[0];
+      if( cnt ) memcpy( f.k_out, s->h_keep, 4UL*cnt );
+      *f.k_cnt = cnt;
+    }
     if( f.do_out ) {   /* chunk-relative offsets -> the batch's numbering; the bytes behind the earlier chunks' */
       ulong const base = *f.d_base, tot = s->h_doff[f.do_n];
       for( ulong j=0; j<=f.do_n; j++ ) f.do_out[j] = base + s->h_doff[j];
@@ -340,10 +385,14 @@ slot_launch_sig( slot_t * s, ulong n, planes_t const & p, schar * err, ulong * t
      the DSM kernel costs the same one launch; after it, the verify launch
      sequence is the untagged call's */
   if( tag && slot_tags( s, n ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  /* survivors: the filter reads the verdicts and the workspace's tag plane where the verify left them */
+  if( s->keep_arm && slot_keep( s, n, s->d_err, (ulong const *)((uint8_t const *)s->d_ws + fd_amd_ws_layout( n ).tag), NULL, NULL ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
   if( slot_done( s ) ) return FD_ED25519_AMD_ERR_DEVICE;
   slot_deliver( s, err, s->h_err, n );
   slot_deliver( s, tag, s->h_tag, 8UL*n );
   s->fl.chk_err = n;
+  s->fl.k_out = s->keep_arm; s->fl.k_cnt = s->kcnt_arm; s->fl.k_n = n;
   s->busy = 1;
   return FD_ED25519_AMD_OK;
 }
@@ -400,8 +449,19 @@ slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, txn_outs_t const & o, ulo
      it rejected the payload, the fail-closed slot mismatch included), then
      one coalesced copy-out that reads the chunk's total on the device: the
      host learns it from h_doff[c] when it drains the slot, without a sync */
+  /* survivors: the filter over the per-transaction verdicts and the tags of
+     the transactions' first slots, gathered into a device plane (not read
+     back from the mapped h_ttag); with descriptors it also leaves the masked
+     footprints, and the pack below runs on those: descriptors for survivors only */
+  uint32_t const * fp = s->d_fp;
+  if( s->keep_arm ) {
+    if( fd_amd_launch_tag_gather( s->d_ktag, s->d_ws, (uint32_t)c, s->d_tbase, s->stream ) ||
+        slot_keep( s, c, s->d_terr, s->d_ktag, o.desc_off ? s->d_fp : NULL, o.desc_off ? s->d_fpk : NULL ) )
+      return FD_ED25519_AMD_ERR_DEVICE;
+    fp = s->d_fpk;
+  }
   if( o.desc_off ) {
-    if( fd_amd_launch_txn_pack( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, s->d_fp, s->d_dbsum, s->d_doff, s->d_desc,
+    if( fd_amd_launch_txn_pack( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, fp, s->d_dbsum, s->d_doff, s->d_desc,
                                 s->desc_stage, s->stream ) ||
         fd_amd_launch_desc_out( s->m_desc, s->d_desc, s->m_doff, s->d_doff, (uint32_t)c, s->desc_stage, desc_bound, s->stream ) )
       return FD_ED25519_AMD_ERR_DEVICE;
@@ -416,6 +476,7 @@ slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, txn_outs_t const & o, ulo
   s->fl.chk_err = (o.sig_err && nslot) ? nslot : 0; s->fl.chk_terr = c;
   s->fl.do_out = o.desc_off; s->fl.do_n = c;
   s->fl.d_out = o.desc; s->fl.d_cap = o.desc_cap; s->fl.d_base = o.dbase;
+  s->fl.k_out = s->keep_arm; s->fl.k_cnt = s->kcnt_arm; s->fl.k_n = c;
   s->busy = 1;
   return FD_ED25519_AMD_OK;
 }
@@ -1419,14 +1480,21 @@ submit_slot( fd_ed25519_amd_t * e, int * rc ) {
 /* Run a stage function once on s as the next submission.  The ticket is
    handed out only when the chunk is in flight.  ERR_INVAL from the stage comes
    before its first launch; any other error quiesces the engine, as in
-   run_ring. */
+   run_ring.  keep / keep_cnt (both or neither: KEEP_ARGS_BAD): a _keep
+   submission, whose launch tail adds the survivor filter; the slot's buffers
+   for it are allocated here, on first use. */
+#define KEEP_ARGS_BAD( keep, keep_cnt ) ( !(keep) != !(keep_cnt) )
+
 template<typename STAGE>
 static int
-submit_run( fd_ed25519_amd_t * e, slot_t * s, ulong * ticket, STAGE stage ) {
+submit_run( fd_ed25519_amd_t * e, slot_t * s, uint * keep, ulong * keep_cnt, ulong * ticket, STAGE stage ) {
+  if( keep ) { int rc = slot_alloc_keep( s, e->cap ); if( rc ) return engine_quiesce( e, rc ); }
   s->ticket = e->ticket + 1UL;
   s->tick_arm = !e->poll_event;
+  s->keep_arm = keep; s->kcnt_arm = keep_cnt;
   long c = stage();
   s->tick_arm = 0;
+  s->keep_arm = NULL; s->kcnt_arm = NULL;
   if( c < 0L ) return c == (long)FD_ED25519_AMD_ERR_INVAL ? FD_ED25519_AMD_ERR_INVAL : engine_quiesce( e, (int)c );
   e->ticket = s->ticket;
   e->a_tail = (e->a_tail + 1) % e->nslot; e->a_cnt++;
@@ -1437,20 +1505,34 @@ submit_run( fd_ed25519_amd_t * e, slot_t * s, ulong * ticket, STAGE stage ) {
 extern "C" int
 fd_ed25519_amd_submit_batch( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
                              void const * const * sig, void const * const * pub, schar * err, ulong * tag, ulong * ticket ) {
-  if( !e || !ticket || !n ) return FD_ED25519_AMD_ERR_INVAL;
+  return fd_ed25519_amd_submit_batch_keep( e, n, msg, sz, sig, pub, err, tag, NULL, NULL, ticket );
+}
+
+extern "C" int
+fd_ed25519_amd_submit_batch_keep( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
+                                  void const * const * sig, void const * const * pub, schar * err, ulong * tag,
+                                  uint * keep, ulong * keep_cnt, ulong * ticket ) {
+  if( !e || !ticket || !n || KEEP_ARGS_BAD( keep, keep_cnt ) ) return FD_ED25519_AMD_ERR_INVAL;
   int rc = batch_args_check( e, n, msg, sz, sig, pub, err );
   if( rc ) return rc;
   slot_t * s = submit_slot( e, &rc );
   if( !s ) return rc;
   if( batch_chunk( e, n, sz ) != n ) return FD_ED25519_AMD_ERR_INVAL;   /* one chunk */
-  return submit_run( e, s, ticket, [&]() -> long { return stage_batch( e, s, n, msg, sz, sig, pub, err, tag ); } );
+  return submit_run( e, s, keep, keep_cnt, ticket, [&]() -> long { return stage_batch( e, s, n, msg, sz, sig, pub, err, tag ); } );
 }
 
 extern "C" int
 fd_ed25519_amd_submit_batch_registered( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
                                         void const * const * sig, void const * const * pub, schar * err, ulong * tag,
                                         ulong * ticket ) {
-  if( !e || !ticket || !n || !msg || !sz || !sig || !pub || !err ) return FD_ED25519_AMD_ERR_INVAL;
+  return fd_ed25519_amd_submit_batch_registered_keep( e, n, msg, sz, sig, pub, err, tag, NULL, NULL, ticket );
+}
+
+extern "C" int
+fd_ed25519_amd_submit_batch_registered_keep( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
+                                             void const * const * sig, void const * const * pub, schar * err, ulong * tag,
+                                             uint * keep, ulong * keep_cnt, ulong * ticket ) {
+  if( !e || !ticket || !n || !msg || !sz || !sig || !pub || !err || KEEP_ARGS_BAD( keep, keep_cnt ) ) return FD_ED25519_AMD_ERR_INVAL;
   reg_view_t view;
   if( !batch_registered_check( e, view, n, msg, sz, sig, pub ) ) return FD_ED25519_AMD_ERR_INVAL;
   int rc;
@@ -1459,7 +1541,7 @@ fd_ed25519_amd_submit_batch_registered( fd_ed25519_amd_t * e, ulong n, void cons
   /* one chunk: the layout over the whole submission, into the free slot's scratch */
   if( n > e->cap || fd_ed25519_amd_gather_layout( n, sz, e->cap, e->blob_cap, slot_gather_dst( e, s ) ) != n )
     return FD_ED25519_AMD_ERR_INVAL;
-  return submit_run( e, s, ticket, [&]() -> long { return stage_batch_registered( e, s, view, n, msg, sz, sig, pub, err, tag ); } );
+  return submit_run( e, s, keep, keep_cnt, ticket, [&]() -> long { return stage_batch_registered( e, s, view, n, msg, sz, sig, pub, err, tag ); } );
 }
 
 extern "C" int
@@ -1467,7 +1549,16 @@ fd_ed25519_amd_submit_txns( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * p
                             uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                             ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
                             ulong * ticket ) {
-  if( !e || !ticket || !txn_cnt ) return FD_ED25519_AMD_ERR_INVAL;
+  return fd_ed25519_amd_submit_txns_keep( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, txn_tag,
+                                          sig_tag, desc_off, desc, desc_cap, NULL, NULL, ticket );
+}
+
+extern "C" int
+fd_ed25519_amd_submit_txns_keep( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
+                                 uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                                 ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
+                                 uint * keep, ulong * keep_cnt, ulong * ticket ) {
+  if( !e || !ticket || !txn_cnt || KEEP_ARGS_BAD( keep, keep_cnt ) ) return FD_ED25519_AMD_ERR_INVAL;
   int rc = fd_amd_txn_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag,
                                   desc_off, desc, desc_cap );
   if( rc ) return rc;
@@ -1478,7 +1569,7 @@ fd_ed25519_amd_submit_txns( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * p
     return FD_ED25519_AMD_ERR_INVAL;   /* one chunk */
   s->a_dbase = 0UL;
   txn_outs_t o = { txn_err, sig_err, txn_tag, sig_tag, desc_off, desc, desc_cap, &s->a_dbase };
-  rc = submit_run( e, s, ticket, [&]() -> long { return stage_txns( e, s, txn_cnt, payload, txn_off, txn_sz, o, &ns ); } );
+  rc = submit_run( e, s, keep, keep_cnt, ticket, [&]() -> long { return stage_txns( e, s, txn_cnt, payload, txn_off, txn_sz, o, &ns ); } );
   /* pure host numbering: the one output a submit call writes */
   if( !rc && sig_base ) fd_ed25519_amd_txn_slots( txn_cnt, payload, txn_off, txn_sz, sig_base );
   return rc;
@@ -1488,7 +1579,16 @@ extern "C" int
 fd_ed25519_amd_submit_txns_registered( fd_ed25519_amd_t * e, ulong txn_cnt, void const * const * txn, ulong const * txn_sz,
                                        schar * txn_err, uint * sig_base, schar * sig_err, ulong * txn_tag, ulong * sig_tag,
                                        ulong * desc_off, uchar * desc, ulong desc_cap, ulong * ticket ) {
-  if( !e || !ticket || !txn_cnt || txn_cnt > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
+  return fd_ed25519_amd_submit_txns_registered_keep( e, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, txn_tag, sig_tag,
+                                                     desc_off, desc, desc_cap, NULL, NULL, ticket );
+}
+
+extern "C" int
+fd_ed25519_amd_submit_txns_registered_keep( fd_ed25519_amd_t * e, ulong txn_cnt, void const * const * txn,
+                                            ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                                            ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
+                                            uint * keep, ulong * keep_cnt, ulong * ticket ) {
+  if( !e || !ticket || !txn_cnt || txn_cnt > 0xFFFFFFFFUL || KEEP_ARGS_BAD( keep, keep_cnt ) ) return FD_ED25519_AMD_ERR_INVAL;
   if( txn_cnt > e->cap ) return FD_ED25519_AMD_ERR_INVAL;   /* one chunk (and it bounds the check's scratch) */
   reg_view_t view;
   std::vector<uint> slots( txn_cnt );
@@ -1503,7 +1603,7 @@ fd_ed25519_amd_submit_txns_registered( fd_ed25519_amd_t * e, ulong txn_cnt, void
     return FD_ED25519_AMD_ERR_INVAL;
   s->a_dbase = 0UL;
   txn_outs_t o = { txn_err, sig_err, txn_tag, sig_tag, desc_off, desc, desc_cap, &s->a_dbase };
-  rc = submit_run( e, s, ticket, [&]() -> long {
+  rc = submit_run( e, s, keep, keep_cnt, ticket, [&]() -> long {
     return stage_txns_registered( e, s, view, txn_cnt, txn, txn_sz, slots.data(), o, &ns );
   } );
   /* pure host numbering: the one output a submit call writes */
@@ -1587,6 +1687,24 @@ fd_ed25519_amd_txn_tags_dev( ulong txn_cnt, uint const * d_tbase, void const * d
   if( !txn_cnt ) return FD_ED25519_AMD_OK;
   if( !d_tbase || !d_ws || !d_txn_tag || ((uintptr_t)d_txn_tag & 7UL) ) return FD_ED25519_AMD_ERR_INVAL;
   if( fd_amd_launch_tag_gather( d_txn_tag, d_ws, (uint32_t)txn_cnt, d_tbase, (hipStream_t)stream ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" ulong
+fd_ed25519_amd_keep_scratch_footprint( ulong n ) {
+  return n > (ulong)FD_AMD_KEEP_MAX ? 0UL : (ulong)fd_amd_keep_layout( n ).total;
+}
+
+extern "C" int
+fd_ed25519_amd_keep_dev( ulong n, schar const * d_err, ulong const * d_tag, uint * d_keep, ulong * d_keep_cnt,
+                         void * d_scratch, ulong salt, void * stream ) {
+  if( n > (ulong)FD_AMD_KEEP_MAX || !d_keep_cnt || ((uintptr_t)d_keep_cnt & 7UL) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( n && ( !d_err || !d_tag || !d_keep || !d_scratch || ((uintptr_t)d_tag & 7UL) || ((uintptr_t)d_keep & 3UL) ||
+             ((uintptr_t)d_scratch & 255UL) ) )
+    return FD_ED25519_AMD_ERR_INVAL;
+  if( fd_amd_launch_keep( (uint32_t)n, (int8_t const *)d_err, (uint64_t const *)d_tag, NULL, NULL, (uint32_t *)d_keep,
+                          (uint64_t *)d_keep_cnt, d_scratch, salt, (hipStream_t)stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
   return FD_ED25519_AMD_OK;
 }
 

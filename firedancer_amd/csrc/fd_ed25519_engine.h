@@ -28,6 +28,9 @@ struct slot_flight_t {
   ulong * do_out; ulong do_n;
   uchar * d_out;  ulong d_cap;
   ulong * d_base;
+  /* survivors (k_out NULL: not asked for): on delivery *k_cnt = h_kcnt[0],
+     at most k_n, and that many entries of h_keep go to k_out */
+  uint *  k_out;  ulong * k_cnt;  ulong k_n;
 };
 
 struct slot_t {
@@ -65,6 +68,22 @@ struct slot_t {
   uint8_t * h_dpack; ulong * h_doff; uint8_t * h_desc;
   void    * m_doff;  void  * m_desc;
   ulong     desc_stage;
+  /* survivors (fd_ed25519_amd_submit_*_keep; allocated by the first
+     submission that asks for them).  d_kpack, one device allocation:
+     d_kscr, the filter's scratch (fd_amd_keep_layout( cap )); d_ktag[cap],
+     the per-transaction tags gathered on the device; d_fpk[cap], the
+     footprint plane masked by the filter, which the descriptor pack then
+     runs on.  h_kpack, one mapped pinned allocation the filter's kernels
+     write: h_kcnt, the count, on a 256-byte line, and h_keep[cap] behind it
+     (m_kcnt / m_keep: their device addresses).  salt: the owning engine's.
+     keep_arm / kcnt_arm: the launch under way is a _keep submission, so the
+     slot's launch tail adds the filter and the drain delivers to them (set
+     and cleared by submit_run, as tick_arm). */
+  uint8_t * d_kpack; void * d_kscr; ulong * d_ktag; uint32_t * d_fpk;
+  uint8_t * h_kpack; ulong * h_kcnt; uint * h_keep;
+  void    * m_kcnt;  void  * m_keep;
+  ulong     salt;
+  uint    * keep_arm; ulong * kcnt_arm;
   /* asynchronous submissions (fd_ed25519_amd_submit_*): the ticket the slot
      carries; its completion word, 8 bytes on a 64-byte line of their own in
      mapped coherent pinned memory, to which k_ticket stores that ticket behind
@@ -100,6 +119,8 @@ struct fd_ed25519_amd {
                         hipEventQuery and no k_ticket is launched (FD_ED25519_AMD_ASYNC_POLL=event: the A/B of
                         tools/async_cost.py) */
   uint8_t * h_tickbuf; /* the slots' completion words, one allocation, 64 bytes each */
+  ulong  salt;         /* the survivor filter's table salt: drawn once at creation from the OS (getrandom; a clock if
+                          that fails), mirrored into every slot */
   slot_t slot[FD_AMD_SLOT_MAX];
 };
 

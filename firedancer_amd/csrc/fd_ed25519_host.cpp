@@ -346,6 +346,33 @@ fd_ed25519_amd_tag( void const * msg, unsigned long sz, void const * sig, void c
   return t;
 }
 
+/* The survivor rule's definition (include/fd_ed25519_amd.h, "Survivors") as
+   pure host code: item i is kept iff err[i] == 0 and ( tag[i] == 0 or no
+   earlier passing item carries tag[i] ).  The tags that passed so far sit in
+   an open-addressed set of at least 2 n slots (0 = empty: tag 0 is never
+   entered).  Writes keep[0, count) only; keep == NULL only counts. */
+unsigned long
+fd_ed25519_amd_keep( unsigned long n, signed char const * err, unsigned long const * tag, unsigned int * keep ) {
+  unsigned long cap = 16UL, cnt = 0UL;
+  while( cap < 2UL*n ) cap <<= 1;
+  std::vector<u64> set( cap, 0UL );
+  for( unsigned long i=0; i<n; i++ ) {
+    if( err[i] ) continue;
+    u64 const t = tag[i];
+    if( t ) {
+      u64 x = t;   /* splitmix64's finalizer */
+      x ^= x >> 30; x *= 0xbf58476d1ce4e5b9UL; x ^= x >> 27; x *= 0x94d049bb133111ebUL; x ^= x >> 31;
+      unsigned long s = x & (cap - 1UL);
+      while( set[s] && set[s] != t ) s = (s + 1UL) & (cap - 1UL);
+      if( set[s] ) continue;   /* an earlier passing item has this tag */
+      set[s] = t;
+    }
+    if( keep ) keep[cnt] = (unsigned int)i;
+    cnt++;
+  }
+  return cnt;
+}
+
 /* Batch keygen + sign over the engine's SoA layout, nthread host threads:
    prv[n][32] -> pub[n][32], sig[n][64] over blob[msg_off[i] .. +msg_sz[i]). */
 int

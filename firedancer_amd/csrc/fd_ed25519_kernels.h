@@ -74,6 +74,10 @@ int fd_amd_launch_txn_reduce( uint32_t txn_cnt, uint32_t const * d_fp, uint32_t 
 int fd_amd_launch_txn_pack( uint32_t txn_cnt, uint8_t const * d_payload, uint32_t const * d_toff, uint32_t const * d_tsz,
                             uint32_t const * d_fp, uint64_t * d_bsum, uint64_t * d_desc_off, uint8_t * d_desc,
                             uint64_t desc_cap, hipStream_t stream );
+/* The scan's first two kernels alone, over any plane of n u32 values (every
+   64 of them summing below 2^32): d_bsum[b] = the sum of the 64-blocks before
+   block b, *d_total = the sum of all; n == 0 writes *d_total = 0 only. */
+int fd_amd_launch_scan64( uint32_t n, uint32_t const * d_val, uint64_t * d_bsum, uint64_t * d_total, hipStream_t stream );
 int fd_amd_launch_desc_out( void * d_dst_mapped, uint8_t const * d_desc, void * d_off_mapped, uint64_t const * d_desc_off,
                             uint32_t txn_cnt, uint64_t cap, uint64_t bound, hipStream_t stream );
 
@@ -222,6 +226,26 @@ int fd_amd_launch_copy_out( void * d_dst_mapped, void const * d_src, size_t n, h
    d_tbase[txn_cnt] slots. */
 int fd_amd_launch_tag_out( void * d_dst, void const * d_ws, size_t n, hipStream_t stream );
 int fd_amd_launch_tag_gather( void * d_dst, void const * d_ws, uint32_t txn_cnt, uint32_t const * d_tbase, hipStream_t stream );
+
+/* Survivors (fd_ed25519_keep.h): d_keep[0 .. *d_keep_cnt) = the ascending
+   indices i < n with d_err[i] == 0 that are the first passing item of their
+   tag d_tag[i] (tag 0: never a duplicate), *d_keep_cnt their number.  d_tag:
+   8-aligned device memory; d_keep (4-aligned, n entries) and d_keep_cnt
+   (8-aligned): device or mapped host memory.  d_scratch: fd_amd_keep_layout(
+   n ).total bytes of device memory, 256-aligned, contents irrelevant.  Writes
+   d_scratch[0, total), d_keep[0, count) and *d_keep_cnt; n == 0 writes
+   *d_keep_cnt = 0 only.  d_fp / d_fpk (both or neither): also d_fpk[i] =
+   d_fp[i] for a survivor, 0 for every other item.  salt: see the header; no
+   output depends on it.  n <= FD_AMD_KEEP_MAX. */
+#define FD_AMD_KEEP_MAX (1u << 30)
+typedef struct {
+  size_t cap;                      /* slots of the table: a power of two >= max( 2 n, 64 ) */
+  size_t key, idx, flag, bsum;     /* byte offsets: u64 [cap], u32 [cap], u32 [n], u64 [ceil( n/64 )] */
+  size_t total;                    /* footprint in bytes */
+} fd_amd_keep_layout_t;
+fd_amd_keep_layout_t fd_amd_keep_layout( size_t n );
+int fd_amd_launch_keep( uint32_t n, int8_t const * d_err, uint64_t const * d_tag, uint32_t const * d_fp, uint32_t * d_fpk,
+                        uint32_t * d_keep, uint64_t * d_keep_cnt, void * d_scratch, uint64_t salt, hipStream_t stream );
 
 /* k_ticket (fd_ed25519_async.hip): one lane stores `ticket` to the 8-aligned
    word at d_word (mapped host memory) with a system-scope release store, behind

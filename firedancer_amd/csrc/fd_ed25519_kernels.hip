@@ -29,6 +29,7 @@
  *   fd_ed25519_tile.h   k_tile_persist, k_tile_synth
  *   fd_ed25519_strict.h k_strict (strict mode's overlay, after the DSM stage)
  *   fd_ed25519_gather.h k_gather, k_gather_txn (pointer-array chunks from registered memory)
+ *   fd_ed25519_keep.h   k_keep_clear, k_keep_insert, k_keep_mark, k_keep_store (a batch's survivors)
  * This file keeps the launch code, the batch-size policy and the small
  * kernels that move results out (k_copy_out: verdicts; k_tag_out /
  * k_tag_gather: the dedup tags k_prep left in the workspace).
@@ -49,6 +50,7 @@
 #include "fd_ed25519_strict.h"
 #include "../../include/fd_txn_amd.h"   /* FD_TXN_AMD_MTU: k_gather_txn's one pass */
 #include "fd_ed25519_gather.h"
+#include "fd_ed25519_keep.h"
 
 /* ------------------------------------------------------------------ */
 /* launch                                                               */

@@ -105,9 +105,10 @@ k_desc_bsum( u32 txn_cnt, u32 const * __restrict__ fp, u64 * __restrict__ bsum )
 }
 
 /* One workgroup: bsum[0, nblk) becomes its own exclusive prefix sum, 64
-   entries per turn of the loop, and desc_off[txn_cnt] the grand total. */
+   entries per turn of the loop, and *total the grand total (the descriptor
+   pack's desc_off[txn_cnt]). */
 __global__ void __launch_bounds__(64)
-k_desc_bscan( u32 nblk, u64 * __restrict__ bsum, u64 * __restrict__ desc_off, u32 txn_cnt ) {
+k_desc_bscan( u32 nblk, u64 * __restrict__ bsum, u64 * __restrict__ total ) {
   u32 lane = threadIdx.x;
   u64 carry = 0UL;
   for( u32 base=0u; base<nblk; base+=64u ) {          /* wave-uniform trip count */
@@ -117,7 +118,7 @@ k_desc_bscan( u32 nblk, u64 * __restrict__ bsum, u64 * __restrict__ desc_off, u3
     if( i < nblk ) bsum[i] = carry + (u64)(incl - v);
     carry += (u64)(u32)__shfl( (int)incl, 63, 64 );
   }
-  if( lane == 0u ) desc_off[txn_cnt] = carry;
+  if( lane == 0u ) *total = carry;
 }
 
 /* desc_off[t] for every transaction, and the descriptor of every accepted
@@ -152,13 +153,23 @@ k_desc_out( u8 * __restrict__ dst, u8 const * __restrict__ src, u64 * __restrict
   if( (no & 1u) && i == 0 ) dst_off[no - 1u] = src_off[no - 1u];
 }
 
+/* The first two steps of the scan, for any plane of n u32 values whose every
+   64-block sums below 2^32: d_bsum[b] = the sum of the blocks before block b,
+   *d_total = the sum of all (n == 0: *d_total = 0 and nothing else). */
+int
+fd_amd_launch_scan64( uint32_t n, uint32_t const * d_val, uint64_t * d_bsum, uint64_t * d_total, hipStream_t stream ) {
+  u32 nblk = (u32)( ( (u64)n + TXN_PACK_BLOCK - 1UL ) / TXN_PACK_BLOCK );
+  if( nblk ) hipLaunchKernelGGL( k_desc_bsum, dim3(nblk), dim3(64), 0, stream, n, d_val, (u64 *)d_bsum );
+  hipLaunchKernelGGL( k_desc_bscan, dim3(1), dim3(64), 0, stream, nblk, (u64 *)d_bsum, (u64 *)d_total );
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int
 fd_amd_launch_txn_pack( uint32_t txn_cnt, uint8_t const * d_payload, uint32_t const * d_toff, uint32_t const * d_tsz,
                         uint32_t const * d_fp, uint64_t * d_bsum, uint64_t * d_desc_off, uint8_t * d_desc,
                         uint64_t desc_cap, hipStream_t stream ) {
   u32 nblk = (u32)( ( (u64)txn_cnt + TXN_PACK_BLOCK - 1UL ) / TXN_PACK_BLOCK );
-  if( nblk ) hipLaunchKernelGGL( k_desc_bsum, dim3(nblk), dim3(64), 0, stream, txn_cnt, d_fp, (u64 *)d_bsum );
-  hipLaunchKernelGGL( k_desc_bscan, dim3(1), dim3(64), 0, stream, nblk, (u64 *)d_bsum, (u64 *)d_desc_off, txn_cnt );
+  if( fd_amd_launch_scan64( txn_cnt, d_fp, d_bsum, d_desc_off + txn_cnt, stream ) ) return -1;
   if( nblk ) hipLaunchKernelGGL( k_desc_store, dim3(nblk), dim3(64), 0, stream, txn_cnt, d_payload, d_toff, d_tsz, d_fp,
                                  (u64 const *)d_bsum, (u64 *)d_desc_off, d_desc, (u64)desc_cap );
   return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -183,6 +183,14 @@ def lib():
            "fd_ed25519_amd_submit_txns": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp, vp, vp, ul, c_ulong_p], i),
            "fd_ed25519_amd_submit_txns_registered": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, ul, c_ulong_p], i),
            "fd_ed25519_amd_async_poll": ([vp, c_ulong_p], i), "fd_ed25519_amd_async_wait": ([vp, c_ulong_p], i),
+           # survivors: in-batch dedup and the verdict filter
+           "fd_ed25519_amd_keep": ([ul, vp, vp, vp], ul),
+           "fd_ed25519_amd_keep_scratch_footprint": ([ul], ul),
+           "fd_ed25519_amd_keep_dev": ([ul, vp, vp, vp, vp, vp, ul, vp], i),
+           "fd_ed25519_amd_submit_batch_keep": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, c_ulong_p], i),
+           "fd_ed25519_amd_submit_batch_registered_keep": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, c_ulong_p], i),
+           "fd_ed25519_amd_submit_txns_keep": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, c_ulong_p], i),
+           "fd_ed25519_amd_submit_txns_registered_keep": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, c_ulong_p], i),
            # the streaming tile's verdict mode
            "fd_verify_amd_tile_set_verdict_mode": ([vp, i], i), "fd_verify_amd_tile_verdict_mode": ([vp], i),
            # debug: k_dsmp's grid, the parked R'
@@ -289,6 +297,36 @@ def tag(msg, sig, public_key):
     return int(lib().fd_ed25519_amd_tag(m if m else None, len(m), s, p))
 
 
+def keep(err, tag):
+    """fd_ed25519_amd_keep: the survivor rule on the host (no device).  The
+    ascending indices (uint32) of the items with err == 0 that are the first
+    passing item of their tag; tag 0 is never a duplicate.  What a want_keep
+    submission delivers from the GPU."""
+    e = np.ascontiguousarray(err, np.int8)
+    t = np.ascontiguousarray(tag, np.uint64)
+    n = int(e.size)
+    assert t.size == n
+    out = np.zeros(max(n, 1), np.uint32)
+    cnt = int(lib().fd_ed25519_amd_keep(n, _ptr(e), _ptr(t), _ptr(out)))
+    return out[:cnt]
+
+
+class _Keep:
+    """The survivor outputs of one want_keep submission, alive until it is
+    delivered: args() is the (keep, keep_cnt) pair of the _keep submit calls
+    (NULL, NULL when not asked for), result() keep[:keep_cnt]."""
+
+    def __init__(self, n, want):
+        self.keep = np.zeros(max(n, 1), np.uint32) if want else None
+        self.cnt = np.zeros(1, np.uint64) if want else None
+
+    def args(self):
+        return (_ptr(self.keep), _ptr(self.cnt)) if self.keep is not None else (None, None)
+
+    def result(self):
+        return self.keep[:int(self.cnt[0])]
+
+
 # ---------------------------------------------------------------- batch engine
 
 class EngineError(RuntimeError):
@@ -385,14 +423,16 @@ class Engine:
         self._pending[int(ticket.value)] = (finish, keep)
         return int(ticket.value)
 
-    def submit_batch_ptrs(self, pub_ptr, sig_ptr, msg_ptr, msg_sz, want_tags=False, registered=True):
+    def submit_batch_ptrs(self, pub_ptr, sig_ptr, msg_ptr, msg_sz, want_tags=False, registered=True, want_keep=False):
         """fd_ed25519_amd_submit_batch_registered (registered=False:
         fd_ed25519_amd_submit_batch, which copies the bytes behind the
         pointers before it returns): verify_batch_ptrs as one chunk, launched
         now and delivered by poll() / wait().  Returns the ticket; raises
         EngineBusy with async_depth submissions in flight, EngineError when the
         batch is empty or exceeds one chunk.  Registered: the bytes behind the
-        pointers must stay valid until delivery."""
+        pointers must stay valid until delivery.  want_keep (the _keep form of
+        either call): the delivered result is a tuple that ends with keep, the
+        uint32 indices of the survivors (module function keep), ascending."""
         pp = np.ascontiguousarray(pub_ptr, np.uint64)
         sp = np.ascontiguousarray(sig_ptr, np.uint64)
         mp = np.ascontiguousarray(msg_ptr, np.uint64)
@@ -403,27 +443,37 @@ class Engine:
         tags = np.zeros(max(n, 1), np.uint64) if want_tags else None
         name = "fd_ed25519_amd_submit_batch_registered" if registered else "fd_ed25519_amd_submit_batch"
         t = ctypes.c_ulong(0)
-        rc = getattr(lib(), name)(self._h, n, _ptr(mp), _ptr(sz), _ptr(sp), _ptr(pp), _ptr(err),
-                                  _ptr(tags) if want_tags else None, ctypes.byref(t))
-        return self._submitted(name, rc, t, lambda: (err[:n], tags[:n]) if want_tags else err[:n],
-                               (pub_ptr, sig_ptr, msg_ptr) if registered else None)
+        args = (self._h, n, _ptr(mp), _ptr(sz), _ptr(sp), _ptr(pp), _ptr(err), _ptr(tags) if want_tags else None)
+        if want_keep:
+            name, k = name + "_keep", _Keep(n, True)
+            rc = getattr(lib(), name)(*args, *k.args(), ctypes.byref(t))
+            finish = lambda: (err[:n], tags[:n], k.result()) if want_tags else (err[:n], k.result())
+        else:
+            rc = getattr(lib(), name)(*args, ctypes.byref(t))
+            finish = lambda: (err[:n], tags[:n]) if want_tags else err[:n]
+        return self._submitted(name, rc, t, finish, (pub_ptr, sig_ptr, msg_ptr) if registered else None)
 
-    def submit_batch(self, msgs, sigs, pubs, want_tags=False):
+    def submit_batch(self, msgs, sigs, pubs, want_tags=False, want_keep=False):
         """verify_batch (lists of bytes-like) as a submission: staged, every
-        byte copied before it returns.  Returns the ticket."""
+        byte copied before it returns.  Returns the ticket.  want_keep: as
+        submit_batch_ptrs."""
         n = len(msgs)
         keep = [bytes(m) for m in msgs] + [bytes(s) for s in sigs] + [bytes(p) for p in pubs]
         bufs = [ctypes.create_string_buffer(b, max(len(b), 1)) for b in keep]
         addr = np.array([ctypes.addressof(b) for b in bufs], np.uint64)
         return self.submit_batch_ptrs(addr[2 * n:], addr[n:2 * n], addr[:n], [len(b) for b in keep[:n]],
-                                      want_tags=want_tags, registered=False)
+                                      want_tags=want_tags, registered=False, want_keep=want_keep)
 
-    def submit_txns_ptrs(self, txn_ptr, txn_sz, want_sigs=False, want_tags=False, want_desc=False, registered=True):
+    def submit_txns_ptrs(self, txn_ptr, txn_sz, want_sigs=False, want_tags=False, want_desc=False, registered=True,
+                         want_keep=False):
         """fd_ed25519_amd_submit_txns_registered: verify_txns_ptrs as one
         chunk, launched now and delivered by poll() / wait(); the payloads must
         stay valid until then.  registered=False: the payloads are copied here
         and go through fd_ed25519_amd_submit_txns (submit_txns).  Returns the
-        ticket."""
+        ticket.  want_keep (fd_ed25519_amd_submit_txns_registered_keep): the
+        delivered tuple ends with keep, the uint32 indices of the surviving
+        transactions, ascending; with want_desc the descriptors are then those
+        of the survivors only."""
         tp = np.ascontiguousarray(txn_ptr, np.uint64)
         sz = np.ascontiguousarray(txn_sz, np.uint64)
         n = int(tp.size)
@@ -434,27 +484,29 @@ class Engine:
             pays = [ctypes.string_at(int(p), int(z)) if z else b"" for p, z in zip(tp.tolist(), sz.tolist())]
             off = np.concatenate(([0], np.cumsum(sz)[:-1])).astype(np.uint32) if n else np.zeros(0, np.uint32)
             return self.submit_txns(np.frombuffer(b"".join(pays), np.uint8), off, sz.astype(np.uint32),
-                                    want_sigs=want_sigs, want_tags=want_tags, want_desc=want_desc)
+                                    want_sigs=want_sigs, want_tags=want_tags, want_desc=want_desc, want_keep=want_keep)
         base, tot = txn_slots_ptrs(tp, sz) if (want_sigs or want_tags) else (None, 0)
-        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc)
+        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc, want_keep)
         t = ctypes.c_ulong(0)
-        rc = lib().fd_ed25519_amd_submit_txns_registered(self._h, n, _ptr(tp), _ptr(sz), *o.args(), ctypes.byref(t))
-        return self._submitted("fd_ed25519_amd_submit_txns_registered", rc, t, o.result, txn_ptr)
+        name = "fd_ed25519_amd_submit_txns_registered" + ("_keep" if want_keep else "")
+        rc = getattr(lib(), name)(self._h, n, _ptr(tp), _ptr(sz), *o.args(), ctypes.byref(t))
+        return self._submitted(name, rc, t, o.result, txn_ptr)
 
-    def submit_txns(self, payload, txn_off, txn_sz, want_sigs=False, want_tags=False, want_desc=False):
+    def submit_txns(self, payload, txn_off, txn_sz, want_sigs=False, want_tags=False, want_desc=False, want_keep=False):
         """fd_ed25519_amd_submit_txns: verify_txns as one chunk, the payload
         bytes copied before it returns, delivered by poll() / wait().  Returns
-        the ticket."""
+        the ticket.  want_keep (fd_ed25519_amd_submit_txns_keep): as
+        submit_txns_ptrs."""
         payload = np.ascontiguousarray(payload, np.uint8)
         off = np.ascontiguousarray(txn_off, np.uint32)
         sz = np.ascontiguousarray(txn_sz, np.uint32)
         n = int(off.size)
         base, tot = txn_slots(payload, off, sz) if (want_sigs or want_tags) else (None, 0)
-        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc)
+        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc, want_keep)
         t = ctypes.c_ulong(0)
-        rc = lib().fd_ed25519_amd_submit_txns(self._h, n, _ptr(payload), _ptr(off), _ptr(sz), int(payload.size), *o.args(),
-                                              ctypes.byref(t))
-        return self._submitted("fd_ed25519_amd_submit_txns", rc, t, o.result, None)
+        name = "fd_ed25519_amd_submit_txns" + ("_keep" if want_keep else "")
+        rc = getattr(lib(), name)(self._h, n, _ptr(payload), _ptr(off), _ptr(sz), int(payload.size), *o.args(), ctypes.byref(t))
+        return self._submitted(name, rc, t, o.result, None)
 
     def _collect(self, name):
         t = ctypes.c_ulong(0)
@@ -647,10 +699,12 @@ class Engine:
 class _TxnOutputs:
     """The output arrays of one transaction submission, alive until it is
     delivered: args() is the (txn_err .. desc_cap) run of the submit calls'
-    arguments, result() what verify_txns returns once they are filled."""
+    arguments (want_keep: and keep, keep_cnt of the _keep forms), result()
+    what verify_txns returns once they are filled (want_keep: and keep)."""
 
-    def __init__(self, n, txn_sz, base, tot, want_sigs, want_tags, want_desc):
+    def __init__(self, n, txn_sz, base, tot, want_sigs, want_tags, want_desc, want_keep=False):
         self.n, self.base, self.want = n, base, (want_sigs, want_tags, want_desc)
+        self.k = _Keep(n, True) if want_keep else None
         self.terr = np.zeros(max(n, 1), np.int8)
         self.serr = np.zeros(max(tot, 1), np.int8) if want_sigs else None
         self.ttag = np.zeros(max(n, 1), np.uint64) if want_tags else None
@@ -660,7 +714,7 @@ class _TxnOutputs:
     def args(self):
         p = lambda a: _ptr(a) if a is not None else None
         return (p(self.terr), p(self.base), p(self.serr), p(self.ttag), p(self.stag), p(self.doff), p(self.desc),
-                int(self.desc.size) if self.desc is not None else 0)
+                int(self.desc.size) if self.desc is not None else 0) + (self.k.args() if self.k else ())
 
     def result(self):
         want_sigs, want_tags, want_desc = self.want
@@ -671,6 +725,8 @@ class _TxnOutputs:
             out += (self.ttag[:self.n], self.stag[:int(self.base[-1])])
         if want_desc:
             out += (self.doff, self.desc[:int(self.doff[-1])])
+        if self.k:
+            out += (self.k.result(),)
         return out if len(out) > 1 else out[0]
 
 
@@ -987,6 +1043,23 @@ def tags_dev(n, d_ws, d_tag, stream=0):
     rc = lib().fd_ed25519_amd_tags_dev(int(n), d_ws, d_tag, stream)
     if rc:
         raise EngineError("fd_ed25519_amd_tags_dev rc=%d" % rc)
+
+
+def keep_scratch_footprint(n):
+    """fd_ed25519_amd_keep_scratch_footprint: device scratch bytes of keep_dev for n items."""
+    return int(lib().fd_ed25519_amd_keep_scratch_footprint(int(n)))
+
+
+def keep_dev(n, d_err, d_tag, d_keep, d_keep_cnt, d_scratch, salt=0, stream=0):
+    """fd_ed25519_amd_keep_dev: the survivor filter alone, device-resident --
+    d_keep[0 .. *d_keep_cnt) (uint32) = keep(err, tag) over the n verdicts
+    d_err (int8) and tags d_tag (uint64: what tags_dev / txn_tags_dev
+    produce), *d_keep_cnt (uint64) their number.  d_scratch: at least
+    keep_scratch_footprint(n) bytes, 256-aligned, contents irrelevant.  No
+    output depends on salt.  Enqueued on `stream`, not synchronised."""
+    rc = lib().fd_ed25519_amd_keep_dev(int(n), d_err, d_tag, d_keep, d_keep_cnt, d_scratch, int(salt) & (2**64 - 1), stream)
+    if rc:
+        raise EngineError("fd_ed25519_amd_keep_dev rc=%d" % rc)
 
 
 def txn_tags_dev(txn_cnt, d_tbase, d_ws, d_txn_tag, stream=0):

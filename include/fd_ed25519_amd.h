@@ -381,8 +381,9 @@ fd_ed25519_amd_multi_verify_soa( fd_ed25519_amd_multi_t * multi,
    tag == NULL is exactly the untagged call (nothing more is launched or
    copied); the untagged functions are these with tag == NULL.  Like err,
    tag is written only during the call, and its contents are unspecified
-   when the call returns an error.  In-batch duplicates are not filtered:
-   dedup stays the caller's. */
+   when the call returns an error.  In-batch duplicates are not filtered by
+   these calls: dedup stays the caller's.  (The _keep submissions, "Survivors"
+   below, return the filtered list of one submission.) */
 ulong
 fd_ed25519_amd_tag( void const * msg,
                     ulong        sz,
@@ -563,6 +564,115 @@ fd_ed25519_amd_async_poll( fd_ed25519_amd_t * eng, ulong * ticket );
 
 int
 fd_ed25519_amd_async_wait( fd_ed25519_amd_t * eng, ulong * ticket );
+
+/* ===== Survivors: in-batch dedup and the verdict filter =====
+
+   What a verify tile publishes is not a verdict per input but the inputs
+   that passed and were not seen before.  The _keep submissions return that
+   list for one submission, made on the GPU behind the verify kernels, so the
+   caller's last O(n) pass per batch (drop the failures, find the duplicates
+   with a hash set of its own, build the list to forward) goes away.
+
+   The rule, one definition for every layer.  For n items with verdicts
+   err[i] and tags tag[i] ("Dedup tags" above), item i is a survivor iff
+     1. err[i] == 0, and
+     2. tag[i] == 0, or no j < i has err[j] == 0 and tag[j] == tag[i].
+   Tag 0 is never deduplicated (the tile's FD_TCACHE_TAG_NULL rule).  Only
+   passing items occupy a tag: the tag is SHA-512( R || A || M ) and does not
+   cover s, so a copy with a corrupted s ahead of the valid one does not
+   suppress it.  keep[0 .. keep_cnt) holds the survivors' indices, ascending.
+   The items are signatures (err, tag) in the signature family and
+   transactions (txn_err, txn_tag: the tag of the first signature) in the
+   transaction family (fd_txn_amd.h).  The verdicts are those of the engine's
+   mode at submit: an s-window signature is a survivor in reference mode and
+   not in strict mode.  The dedup window is one submission, which is one
+   chunk.
+
+   fd_ed25519_amd_keep is the rule as pure host code (no device; what a
+   CPU-only caller or a unit test computes): it returns keep_cnt and writes
+   keep[0, keep_cnt) and nothing else; keep == NULL only counts.
+
+   fd_ed25519_amd_keep_dev is the filter alone, device-resident, with the
+   conventions of the other _dev calls (the caller's stream, no sync): d_err
+   and d_tag are n entries of device memory (d_tag 8-aligned: what
+   fd_ed25519_amd_tags_dev / fd_ed25519_amd_txn_tags_dev produce, so a
+   device-resident caller chains the calls it already has); d_keep (n
+   entries, 4-aligned) and d_keep_cnt (8-aligned) are device or mapped host
+   memory; d_scratch is at least fd_ed25519_amd_keep_scratch_footprint( n )
+   bytes of device memory, 256-aligned.  n is at most 2^30 (the footprint of
+   a larger n is 0 and the call returns FD_ED25519_AMD_ERR_INVAL).  Memory,
+   as for fd_ed25519_amd_verify_dev: the scratch may hold anything on entry;
+   the call writes d_scratch[0, footprint( n )), d_keep[0, keep_cnt) and
+   *d_keep_cnt and nothing else; d_err and d_tag are only read; n == 0 writes
+   *d_keep_cnt = 0 only.  Passing items with a nonzero tag meet in an
+   open-addressed table in the scratch (at least 2 n slots); a slot is chosen
+   by a 64-bit mix of tag ^ salt.  Tags are hashes an attacker chooses: with
+   a known slot function it could grind tags into one probe chain and make
+   the filter quadratic, so salt should be a secret (the engine draws its own
+   from the OS once, at creation).  No output depends on salt.  Kernels
+   ordered by the stream; no workgroup ever waits for another.
+
+   The _keep submissions take the arguments of the submit call they are named
+   after plus keep (capacity n / txn_cnt entries) and keep_cnt before ticket.
+   Both NULL is exactly that submit call; one without the other is
+   FD_ED25519_AMD_ERR_INVAL, with the effect of every error return.
+   Everything in "Asynchronous submissions" holds unchanged: one chunk, BUSY,
+   the inputs, ticket order, the error returns, the mode at submit,
+   FD_ED25519_AMD_ASYNC_POLL.  keep[0, keep_cnt) and *keep_cnt are written at
+   delivery, by the poll / wait that reports the ticket; no byte of keep at or
+   beyond keep_cnt is written.  The tags the filter needs are produced on the
+   device whether or not the caller asked for tag; every other output (err,
+   tag) is what the plain submit delivers, for all n items.  The slot's
+   buffers for the filter are allocated by the first submission that asks.
+
+   Out of scope: the synchronous multi-chunk calls and the SoA shapes (a
+   dedup window over several chunks needs the inserts of different streams
+   ordered), the multi-device engine, the streaming tile (which has its own
+   dedup), the drop-in fd_ed25519_verify, and dedup across submissions. */
+ulong
+fd_ed25519_amd_keep( ulong         n,
+                     schar const * err,
+                     ulong const * tag,
+                     uint *        keep );
+
+ulong
+fd_ed25519_amd_keep_scratch_footprint( ulong n );
+
+int
+fd_ed25519_amd_keep_dev( ulong         n,
+                         schar const * d_err,
+                         ulong const * d_tag,
+                         uint *        d_keep,
+                         ulong *       d_keep_cnt,
+                         void *        d_scratch,
+                         ulong         salt,
+                         void *        stream );
+
+int
+fd_ed25519_amd_submit_batch_keep( fd_ed25519_amd_t *   eng,
+                                  ulong                n,
+                                  void const * const * msg,
+                                  ulong const *        sz,
+                                  void const * const * sig,
+                                  void const * const * pub,
+                                  schar *              err,
+                                  ulong *              tag,
+                                  uint *               keep,
+                                  ulong *              keep_cnt,
+                                  ulong *              ticket );
+
+int
+fd_ed25519_amd_submit_batch_registered_keep( fd_ed25519_amd_t *   eng,
+                                             ulong                n,
+                                             void const * const * msg,
+                                             ulong const *        sz,
+                                             void const * const * sig,
+                                             void const * const * pub,
+                                             schar *              err,
+                                             ulong *              tag,
+                                             uint *               keep,
+                                             ulong *              keep_cnt,
+                                             ulong *              ticket );
 
 /* Device-resident batch: every pointer is HIP device memory, already
    resident (the layout of fd_ed25519_amd_verify_soa).  Enqueues the

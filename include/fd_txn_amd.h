@@ -305,8 +305,9 @@ fd_ed25519_amd_verify_txns_registered_tag( fd_ed25519_amd_t *   eng,
 
    Out of scope: the multi-device forms (a shard's base depends on the other
    shards' totals), the streaming tile (its 1408-B output frames have no room
-   for a 3570-B descriptor), the drop-in call, and filtering descriptors by
-   verdict. */
+   for a 3570-B descriptor), the drop-in call, and, in the synchronous calls
+   and the plain submissions, filtering descriptors by verdict (the _keep
+   submissions below pack descriptors for the survivors only). */
 
 /* Upper bound on fd_txn_parse's footprint for ANY payload of payload_sz
    bytes (pure host code): 0 below 134 bytes, the smallest payload that
@@ -462,6 +463,62 @@ fd_ed25519_amd_submit_txns_registered( fd_ed25519_amd_t *   eng,
                                        uchar *              desc,
                                        ulong                desc_cap,
                                        ulong *              ticket );
+
+/* The two submissions above that also return the publish list: "Survivors"
+   in fd_ed25519_amd.h, with transactions as the items -- transaction t is a
+   survivor iff txn_err[t] == 0 and ( its tag, the tag of its first
+   signature, is 0 or no earlier passing transaction of the submission has
+   it ).  keep (capacity txn_cnt) and keep_cnt come before ticket; both NULL
+   is exactly the submit call above, one without the other
+   FD_ED25519_AMD_ERR_INVAL.  Written at delivery: keep[0, keep_cnt), the
+   survivors' indices ascending, and *keep_cnt; nothing at or beyond
+   keep[keep_cnt].
+   - The tags the filter needs are gathered into a device plane whether or
+     not txn_tag was asked for.  txn_err, txn_tag, sig_tag, sig_err and
+     sig_base stay what the submit call above delivers, for all transactions.
+   - Descriptors, when asked for, are packed for the survivors only: desc_off
+     keeps its txn_cnt + 1 entries and its layout, and desc_off[t+1] ==
+     desc_off[t] exactly where t is not a survivor; a survivor's bytes are
+     those the unfiltered call returns for it.  The pack runs behind the
+     filter on the footprints it masked.  desc_cap is still checked against
+     the submission's bound sum.
+   Out of scope, as there: the synchronous calls, the multi-device engine, the
+   tile, dedup across submissions. */
+int
+fd_ed25519_amd_submit_txns_keep( fd_ed25519_amd_t * eng,
+                                 ulong              txn_cnt,
+                                 uchar const *      payload,
+                                 uint const *       txn_off,
+                                 uint const *       txn_sz,
+                                 ulong              payload_sz,
+                                 schar *            txn_err,
+                                 uint *             sig_base,
+                                 schar *            sig_err,
+                                 ulong *            txn_tag,
+                                 ulong *            sig_tag,
+                                 ulong *            desc_off,
+                                 uchar *            desc,
+                                 ulong              desc_cap,
+                                 uint *             keep,
+                                 ulong *            keep_cnt,
+                                 ulong *            ticket );
+
+int
+fd_ed25519_amd_submit_txns_registered_keep( fd_ed25519_amd_t *   eng,
+                                            ulong                txn_cnt,
+                                            void const * const * txn,
+                                            ulong const *        txn_sz,
+                                            schar *              txn_err,
+                                            uint *               sig_base,
+                                            schar *              sig_err,
+                                            ulong *              txn_tag,
+                                            ulong *              sig_tag,
+                                            ulong *              desc_off,
+                                            uchar *              desc,
+                                            ulong                desc_cap,
+                                            uint *               keep,
+                                            ulong *              keep_cnt,
+                                            ulong *              ticket );
 
 /* Signature-slot numbering of a pointer-array batch (pure host code, no
    device): the rule of fd_ed25519_amd_txn_slots, one payload per pointer.
