@@ -27,7 +27,7 @@ LIB_DIAG = os.path.join(PKG, "libfd_ed25519_amd_diag.so")
 ARCH = os.environ.get("FD_AMD_ARCH", "gfx950")
 
 SOURCES = ["fd_ed25519_kernels.hip", "fd_txn_kernels.hip", "fd_ed25519_sign.hip", "fd_ed25519_engine.cpp", "fd_ed25519_multi.cpp", "fd_ed25519_host.cpp",
-           "fd_verify_tile.cpp", "fd_numa.cpp", "fd_ed25519_async.hip"]
+           "fd_verify_tile.cpp", "fd_numa.cpp", "fd_ed25519_async.hip", "fd_ed25519_window.cpp"]
 CONSTS = os.path.join(CSRC, "fd_ed25519_consts.h")
 GEN_CONSTS = os.path.join(ROOT, "tools", "gen_consts.py")
 

@@ -74,6 +74,7 @@ slot_free( slot_t * s ) {
   if( s->h_dpack) (void)hipHostFree( s->h_dpack );
   if( s->d_kpack) (void)hipFree( s->d_kpack );
   if( s->h_kpack) (void)hipHostFree( s->h_kpack );
+  if( s->win_done ) (void)hipEventDestroy( s->win_done );
   if( s->stream ) (void)hipStreamDestroy( s->stream );
   if( s->done   ) (void)hipEventDestroy( s->done );
   memset( s, 0, sizeof(*s) );
@@ -178,6 +179,7 @@ fd_ed25519_amd_delete( fd_ed25519_amd_t * e ) {
   if( !e ) return;
   (void)hipSetDevice( e->device );
   for( int k=0; k<FD_AMD_SLOT_MAX; k++ ) { if( e->slot[k].stream ) (void)hipStreamSynchronize( e->slot[k].stream ); slot_free( &e->slot[k] ); }
+  if( e->win ) { e->win->pend = NULL; e->win->owner = NULL; }   /* the borrowed window: nothing of it is queued any more */
   if( e->h_tickbuf ) (void)hipHostFree( e->h_tickbuf );
   free( e );
 }
@@ -243,7 +245,9 @@ slot_alloc_desc( slot_t * s, ulong cap, ulong blob_cap ) {
 static int
 slot_alloc_keep( slot_t * s, ulong cap ) {
   if( s->d_kpack ) return FD_ED25519_AMD_OK;
-  ulong const scr = fd_amd_keep_layout( cap ).total, pl = ( 8UL*cap + 255UL ) & ~255UL;   /* scr: a multiple of 256 */
+  /* scr: a multiple of 256; the window's planes behind the filter's, used only with a window attached */
+  ulong const scr = fd_amd_win_scratch( cap ).total, pl = ( 8UL*cap + 255UL ) & ~255UL;
+  HIPCHK( hipEventCreateWithFlags( &s->win_done, hipEventDisableTiming ) );
   HIPCHK( hipMalloc( (void **)&s->d_kpack, scr + 2UL*pl ) );
   s->d_kscr = s->d_kpack; s->d_ktag = (ulong *)(s->d_kpack + scr); s->d_fpk = (uint32_t *)(s->d_kpack + scr + pl);
   HIPCHK( hipHostMalloc( (void **)&s->h_kpack, 256UL + 4UL*cap, hipHostMallocMapped | hipHostMallocCoherent ) );
@@ -257,11 +261,21 @@ slot_alloc_keep( slot_t * s, ulong cap ) {
    survivors of the chunk's n items, from their verdicts d_err (in the
    engine's mode: behind k_strict) and tags d_tag, both on the device, into
    the mapped h_keep / h_kcnt -- written in place by the filter's last
-   kernels, as the verdicts are by slot_out.  fp / fpk: fd_amd_launch_keep's. */
+   kernels, as the verdicts are by slot_out.  fp / fpk: fd_amd_launch_keep's.
+   With a window attached the step also filters against it and feeds it.
+   Submissions act on the window in ticket order, which is the order of
+   these calls: the window's kernels wait for the event the previous
+   submission recorded behind its own (on another slot's stream; everything
+   ahead of them still overlaps) and the slot's is recorded behind them. */
 static int
 slot_keep( slot_t * s, ulong n, int8_t const * d_err, ulong const * d_tag, uint32_t const * fp, uint32_t * fpk ) {
-  return fd_amd_launch_keep( (uint32_t)n, d_err, (uint64_t const *)d_tag, fp, fpk, (uint32_t *)s->m_keep, (uint64_t *)s->m_kcnt,
-                             s->d_kscr, s->salt, s->stream ) ? FD_ED25519_AMD_ERR_DEVICE : FD_ED25519_AMD_OK;
+  fd_ed25519_amd_window_t * w = s->win_arm;
+  if( !w )
+    return fd_amd_launch_keep( (uint32_t)n, d_err, (uint64_t const *)d_tag, fp, fpk, (uint32_t *)s->m_keep, (uint64_t *)s->m_kcnt,
+                               s->d_kscr, s->salt, s->stream ) ? FD_ED25519_AMD_ERR_DEVICE : FD_ED25519_AMD_OK;
+  fd_amd_win_dev_t d = fd_amd_window_arm( w, n, s->win_done );
+  return fd_amd_launch_keep_win( (uint32_t)n, d_err, (uint64_t const *)d_tag, fp, fpk, (uint32_t *)s->m_keep, (uint64_t *)s->m_kcnt,
+                                 s->d_kscr, s->salt, &d, s->stream ) ? FD_ED25519_AMD_ERR_DEVICE : FD_ED25519_AMD_OK;
 }
 
 /* The n tags of the chunk just verified on s (the tag plane of its
@@ -1491,10 +1505,10 @@ submit_run( fd_ed25519_amd_t * e, slot_t * s, uint * keep, ulong * keep_cnt, ulo
   if( keep ) { int rc = slot_alloc_keep( s, e->cap ); if( rc ) return engine_quiesce( e, rc ); }
   s->ticket = e->ticket + 1UL;
   s->tick_arm = !e->poll_event;
-  s->keep_arm = keep; s->kcnt_arm = keep_cnt;
+  s->keep_arm = keep; s->kcnt_arm = keep_cnt; s->win_arm = keep ? e->win : NULL;
   long c = stage();
   s->tick_arm = 0;
-  s->keep_arm = NULL; s->kcnt_arm = NULL;
+  s->keep_arm = NULL; s->kcnt_arm = NULL; s->win_arm = NULL;
   if( c < 0L ) return c == (long)FD_ED25519_AMD_ERR_INVAL ? FD_ED25519_AMD_ERR_INVAL : engine_quiesce( e, (int)c );
   e->ticket = s->ticket;
   e->a_tail = (e->a_tail + 1) % e->nslot; e->a_cnt++;
@@ -1661,6 +1675,23 @@ extern "C" int
 fd_ed25519_amd_mode( fd_ed25519_amd_t const * e ) {
   return e ? e->mode : FD_ED25519_AMD_ERR_INVAL;
 }
+
+/* The engine borrows w (NULL: gives its window back).  With nothing in
+   flight every event recorded on the old window's behalf has fired, so it
+   leaves with nothing queued. */
+extern "C" int
+fd_ed25519_amd_set_window( fd_ed25519_amd_t * e, fd_ed25519_amd_window_t * w ) {
+  if( !e || e->a_cnt ) return FD_ED25519_AMD_ERR_INVAL;
+  if( w && ( w->device != e->device || w->depth < e->cap || ( w->owner && w->owner != e ) ) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( e->win == w ) return FD_ED25519_AMD_OK;
+  if( e->win ) { e->win->pend = NULL; e->win->owner = NULL; }
+  e->win = w;
+  if( w ) w->owner = e;
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" fd_ed25519_amd_window_t *
+fd_ed25519_amd_window( fd_ed25519_amd_t const * e ) { return e ? e->win : NULL; }
 
 extern "C" int
 fd_ed25519_amd_work_stats_dev( ulong n, void const * d_ws, uint * d_stats, void * stream ) {

@@ -84,6 +84,13 @@ struct slot_t {
   void    * m_kcnt;  void  * m_keep;
   ulong     salt;
   uint    * keep_arm; ulong * kcnt_arm;
+  /* the dedup window (fd_ed25519_amd_set_window): win_arm, the engine's
+     window while a _keep submission is being launched (NULL: none attached),
+     so the filter step runs against it; win_done, recorded behind that step
+     (created with the survivor buffers): the next _keep submission's stream,
+     on whichever slot, waits for it ahead of its own filter step */
+  fd_ed25519_amd_window_t * win_arm;
+  hipEvent_t win_done;
   /* asynchronous submissions (fd_ed25519_amd_submit_*): the ticket the slot
      carries; its completion word, 8 bytes on a 64-byte line of their own in
      mapped coherent pinned memory, to which k_ticket stores that ticket behind
@@ -121,8 +128,54 @@ struct fd_ed25519_amd {
   uint8_t * h_tickbuf; /* the slots' completion words, one allocation, 64 bytes each */
   ulong  salt;         /* the survivor filter's table salt: drawn once at creation from the OS (getrandom; a clock if
                           that fails), mirrored into every slot */
+  fd_ed25519_amd_window_t * win;   /* the dedup window the _keep submissions filter against and feed (borrowed; NULL: none) */
   slot_t slot[FD_AMD_SLOT_MAX];
 };
+
+/* A dedup window (fd_ed25519_window.cpp; include/fd_ed25519_amd.h, "The
+   dedup window").  device < 0: host-only, the state lives in h_ring / h_key /
+   h_stamp and fd_ed25519_amd_window_keep runs the rule on it.  Otherwise the
+   same four arrays lie in d_state (fd_amd_win_layout( depth )) and only the
+   kernels of fd_ed25519_window.h touch them.  since: the items offered since
+   the map was last rebuilt (the host's bound on the keys it holds beyond the
+   live ones).  seq: the submissions that acted on a device window, whose
+   parity says which head word holds the count.  owner: the engine the window is attached to.  pend: the event
+   recorded behind the last launch that touched the window (own_ev for
+   fd_ed25519_amd_window_keep_dev, a slot's win_done for an engine's
+   submission), NULL when nothing is queued. */
+struct fd_ed25519_amd_window_s {
+  int     device;
+  ulong   depth, salt, cap, since, seq;
+  ulong * h_ring; ulong * h_key; ulong * h_stamp; ulong h_head;
+  uint8_t * d_state;
+  struct fd_ed25519_amd * owner;
+  hipEvent_t own_ev, pend;
+};
+
+#ifdef FD_ED25519_KERNELS_H
+/* The launch's view of a device window for a submission of n items, which
+   it counts into `since`: a rebuild goes first whenever the items offered
+   since the last one, these included, exceed depth.  n > 0 is a submission
+   and takes the next head word; n == 0 (import's rebuild) stays on this one.
+   done: the event to record behind the window's kernels; it becomes the
+   window's pending one, and the one pending now is waited for unless it is
+   the same (then the stream orders the two). */
+static inline fd_amd_win_dev_t
+fd_amd_window_arm( fd_ed25519_amd_window_t * w, ulong n, hipEvent_t done ) {
+  fd_amd_win_layout_t L = fd_amd_win_layout( w->depth );
+  fd_amd_win_dev_t d;
+  d.ring = (uint64_t *)(w->d_state + L.ring); d.head  = (uint64_t *)(w->d_state + L.head);
+  d.key  = (uint64_t *)(w->d_state + L.key);  d.stamp = (uint64_t *)(w->d_state + L.stamp);
+  d.depth = w->depth; d.salt = w->salt; d.cap = (uint32_t)L.cap;
+  d.rebuild = w->since + n > w->depth;
+  w->since = d.rebuild ? n : w->since + n;
+  d.cur = (uint32_t)( w->seq & 1UL );
+  if( n ) w->seq++;
+  d.wait = w->pend != done ? w->pend : NULL; d.done = done;
+  if( done ) w->pend = done;
+  return d;
+}
+#endif
 
 /* NUMA placement (fd_numa.cpp): bind the calling thread to the device's
    node (CPUs + preferred memory), or prefer it only while allocating. */

@@ -133,20 +133,36 @@ fd_amd_keep_layout( size_t n ) {
   return L;
 }
 
+/* the window's stages (fd_ed25519_window.h, included behind this file) */
+static int win_launch_step( fd_amd_win_dev_t const * w, u32 n, u64 const * tag, u32 * flag, u32 * flag2, u64 * bsum2, u32 * fpk,
+                            hipStream_t stream );
+
 int
 fd_amd_launch_keep( uint32_t n, int8_t const * d_err, uint64_t const * d_tag, uint32_t const * d_fp, uint32_t * d_fpk,
                     uint32_t * d_keep, uint64_t * d_keep_cnt, void * d_scratch, uint64_t salt, hipStream_t stream ) {
-  if( n > FD_AMD_KEEP_MAX ) return -1;
+  return fd_amd_launch_keep_win( n, d_err, d_tag, d_fp, d_fpk, d_keep, d_keep_cnt, d_scratch, salt, NULL, stream );
+}
+
+/* w == NULL: the launches above and nothing else.  With a window, and n > 0,
+   its step goes between k_keep_mark and the scan; the scratch is then
+   fd_amd_win_scratch( n ). */
+int
+fd_amd_launch_keep_win( uint32_t n, int8_t const * d_err, uint64_t const * d_tag, uint32_t const * d_fp, uint32_t * d_fpk,
+                        uint32_t * d_keep, uint64_t * d_keep_cnt, void * d_scratch, uint64_t salt,
+                        fd_amd_win_dev_t const * w, hipStream_t stream ) {
+  if( n > FD_AMD_KEEP_MAX || ( w && (uint64_t)n > w->depth ) ) return -1;
   fd_amd_keep_layout_t L = fd_amd_keep_layout( n );
-  u8 * w = (u8 *)d_scratch;
-  u64 * key = (u64 *)(w + L.key), * bsum = (u64 *)(w + L.bsum);
-  u32 * idx = (u32 *)(w + L.idx), * flag = (u32 *)(w + L.flag);
+  fd_amd_win_scratch_t S = fd_amd_win_scratch( n );
+  u8 * w8 = (u8 *)d_scratch;
+  u64 * key = (u64 *)(w8 + L.key), * bsum = (u64 *)(w8 + L.bsum);
+  u32 * idx = (u32 *)(w8 + L.idx), * flag = (u32 *)(w8 + L.flag);
   u32 const cap = (u32)L.cap;
   if( n ) {
     hipLaunchKernelGGL( k_keep_clear,  dim3(cap/256u ? cap/256u : 1u), dim3(256), 0, stream, key, idx, cap );
     hipLaunchKernelGGL( k_keep_insert, dim3((n + 255u)/256u), dim3(256), 0, stream, n, d_err, (u64 const *)d_tag, key, idx, cap, (u64)salt );
     hipLaunchKernelGGL( k_keep_mark,   dim3((n + 255u)/256u), dim3(256), 0, stream, n, d_err, (u64 const *)d_tag, (u64 const *)key,
                         (u32 const *)idx, cap, (u64)salt, flag, d_fp, d_fpk );
+    if( w && win_launch_step( w, n, (u64 const *)d_tag, flag, (u32 *)(w8 + S.flag2), (u64 *)(w8 + S.bsum2), d_fpk, stream ) ) return -1;
   }
   if( fd_amd_launch_scan64( n, flag, bsum, d_keep_cnt, stream ) ) return -1;   /* n == 0: *d_keep_cnt = 0 and nothing else */
   if( n ) hipLaunchKernelGGL( k_keep_store, dim3((n + TXN_PACK_BLOCK - 1u)/TXN_PACK_BLOCK), dim3(64), 0, stream, n, (u32 const *)flag,

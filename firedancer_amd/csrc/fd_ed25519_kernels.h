@@ -247,6 +247,38 @@ fd_amd_keep_layout_t fd_amd_keep_layout( size_t n );
 int fd_amd_launch_keep( uint32_t n, int8_t const * d_err, uint64_t const * d_tag, uint32_t const * d_fp, uint32_t * d_fpk,
                         uint32_t * d_keep, uint64_t * d_keep_cnt, void * d_scratch, uint64_t salt, hipStream_t stream );
 
+/* The dedup window (fd_ed25519_window.h): the survivors of a submission
+   filtered against the last `depth` tags earlier submissions published, which
+   are then joined by this one's.  fd_amd_win_dev_t: where a window's state
+   lies on the device (fd_amd_win_layout( depth ): ring u64 [depth], head u64
+   [2], key and stamp u64 [cap], cap a power of two >= max( 4 depth, 256 )),
+   its salt, which head word this launch reads (cur: it leaves the new count
+   in the other), whether the host wants the map rebuilt ahead of this launch,
+   the event to wait for ahead of the window's kernels and the one to record
+   behind them (NULL: none).
+   fd_amd_launch_keep_win is fd_amd_launch_keep with a window (w == NULL: that
+   call exactly): n <= w->depth, and d_scratch holds fd_amd_win_scratch( n )
+   .total bytes -- the keep layout first, then flag2 u32 [n] and bsum2 u64
+   [ceil( n/64 )].  n == 0 touches no window.  Launches on
+   one window must be ordered by the caller (one stream, or events).
+   fd_amd_launch_win_rebuild: the rebuild alone (after an import wrote ring
+   and head[cur]). */
+typedef struct {
+  uint64_t * ring; uint64_t * head; uint64_t * key; uint64_t * stamp;
+  uint64_t   depth, salt;
+  uint32_t   cap, cur;
+  int        rebuild;
+  hipEvent_t wait, done;
+} fd_amd_win_dev_t;
+typedef struct { size_t cap, ring, head, key, stamp, total; } fd_amd_win_layout_t;
+typedef struct { size_t flag2, bsum2, total; } fd_amd_win_scratch_t;
+fd_amd_win_layout_t  fd_amd_win_layout( size_t depth );
+fd_amd_win_scratch_t fd_amd_win_scratch( size_t n );
+int fd_amd_launch_win_rebuild( fd_amd_win_dev_t const * w, hipStream_t stream );
+int fd_amd_launch_keep_win( uint32_t n, int8_t const * d_err, uint64_t const * d_tag, uint32_t const * d_fp, uint32_t * d_fpk,
+                            uint32_t * d_keep, uint64_t * d_keep_cnt, void * d_scratch, uint64_t salt,
+                            fd_amd_win_dev_t const * w, hipStream_t stream );
+
 /* k_ticket (fd_ed25519_async.hip): one lane stores `ticket` to the 8-aligned
    word at d_word (mapped host memory) with a system-scope release store, behind
    whatever the stream holds. */

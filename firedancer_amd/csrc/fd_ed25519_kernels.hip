@@ -30,6 +30,7 @@
  *   fd_ed25519_strict.h k_strict (strict mode's overlay, after the DSM stage)
  *   fd_ed25519_gather.h k_gather, k_gather_txn (pointer-array chunks from registered memory)
  *   fd_ed25519_keep.h   k_keep_clear, k_keep_insert, k_keep_mark, k_keep_store (a batch's survivors)
+ *   fd_ed25519_window.h k_win_clear, k_win_rebuild, k_win_query, k_win_insert, k_win_head (dedup across submissions)
  * This file keeps the launch code, the batch-size policy and the small
  * kernels that move results out (k_copy_out: verdicts; k_tag_out /
  * k_tag_gather: the dedup tags k_prep left in the workspace).
@@ -51,6 +52,7 @@
 #include "../../include/fd_txn_amd.h"   /* FD_TXN_AMD_MTU: k_gather_txn's one pass */
 #include "fd_ed25519_gather.h"
 #include "fd_ed25519_keep.h"
+#include "fd_ed25519_window.h"
 
 /* ------------------------------------------------------------------ */
 /* launch                                                               */

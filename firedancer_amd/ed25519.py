@@ -191,6 +191,14 @@ def lib():
            "fd_ed25519_amd_submit_batch_registered_keep": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, c_ulong_p], i),
            "fd_ed25519_amd_submit_txns_keep": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, c_ulong_p], i),
            "fd_ed25519_amd_submit_txns_registered_keep": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, c_ulong_p], i),
+           # the dedup window: dedup across submissions
+           "fd_ed25519_amd_window_new": ([i, ul, ul], vp), "fd_ed25519_amd_window_delete": ([vp], None),
+           "fd_ed25519_amd_window_depth": ([vp], ul),
+           "fd_ed25519_amd_window_keep": ([vp, ul, vp, vp, vp], ul),
+           "fd_ed25519_amd_window_keep_scratch_footprint": ([ul], ul),
+           "fd_ed25519_amd_window_keep_dev": ([vp, ul, vp, vp, vp, vp, vp, vp], i),
+           "fd_ed25519_amd_window_export": ([vp, vp], ul), "fd_ed25519_amd_window_import": ([vp, vp, ul], i),
+           "fd_ed25519_amd_set_window": ([vp, vp], i), "fd_ed25519_amd_window": ([vp], vp),
            # the streaming tile's verdict mode
            "fd_verify_amd_tile_set_verdict_mode": ([vp, i], i), "fd_verify_amd_tile_verdict_mode": ([vp], i),
            # debug: k_dsmp's grid, the parked R'
@@ -333,6 +341,75 @@ class EngineError(RuntimeError):
     pass
 
 
+WINDOW_DEPTH_MAX = 1 << 22   # FD_ED25519_AMD_WINDOW_DEPTH_MAX
+
+
+class Window:
+    """fd_ed25519_amd_window_t: the last `depth` tags a caller published
+    (include/fd_ed25519_amd.h, "The dedup window").  device < 0: host-only
+    (keep); otherwise device-resident (keep_dev, or Engine.set_window).
+    salt 0: drawn from the OS; no output depends on it."""
+
+    def __init__(self, device, depth, salt=0):
+        self._h = lib().fd_ed25519_amd_window_new(int(device), int(depth), int(salt) & (2**64 - 1))
+        if not self._h:
+            raise EngineError("fd_ed25519_amd_window_new(device=%d, depth=%d) failed" % (device, depth))
+        self.device, self.depth = int(device), int(lib().fd_ed25519_amd_window_depth(self._h))
+
+    def keep(self, err, tag):
+        """fd_ed25519_amd_window_keep (host-only window): one submission; the
+        survivors' indices (uint32), ascending."""
+        e = np.ascontiguousarray(err, np.int8)
+        t = np.ascontiguousarray(tag, np.uint64)
+        n = int(e.size)
+        assert t.size == n
+        out = np.zeros(max(n, 1), np.uint32)
+        cnt = int(lib().fd_ed25519_amd_window_keep(self._h, n, _ptr(e), _ptr(t), _ptr(out)))
+        if cnt == 2**64 - 1:
+            raise EngineError("fd_ed25519_amd_window_keep(n=%d) refused (n > depth %d, or a device window)" % (n, self.depth))
+        return out[:cnt]
+
+    def keep_dev(self, n, d_err, d_tag, d_keep, d_keep_cnt, d_scratch, stream=0):
+        """fd_ed25519_amd_window_keep_dev: keep_dev's arguments; d_scratch
+        holds window_keep_scratch_footprint(n) bytes.  No sync."""
+        rc = lib().fd_ed25519_amd_window_keep_dev(self._h, int(n), d_err, d_tag, d_keep, d_keep_cnt, d_scratch, stream)
+        if rc:
+            raise EngineError("fd_ed25519_amd_window_keep_dev rc=%d" % rc)
+
+    def export(self):
+        """fd_ed25519_amd_window_export: the live tags (uint64), oldest first;
+        waits for the window's queued work."""
+        out = np.zeros(self.depth, np.uint64)
+        cnt = int(lib().fd_ed25519_amd_window_export(self._h, _ptr(out)))
+        if cnt > self.depth:
+            raise EngineError("fd_ed25519_amd_window_export failed")
+        return out[:cnt].copy()
+
+    def load(self, tags):
+        """fd_ed25519_amd_window_import: replace the contents with tags
+        (nonzero, distinct, oldest first, at most depth); none: a reset."""
+        t = np.ascontiguousarray(tags, np.uint64)
+        rc = lib().fd_ed25519_amd_window_import(self._h, _ptr(t), int(t.size))
+        if rc:
+            raise EngineError("fd_ed25519_amd_window_import(cnt=%d) rc=%d" % (t.size, rc))
+
+    def close(self):
+        if self._h:
+            lib().fd_ed25519_amd_window_delete(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def window_keep_scratch_footprint(n):
+    """fd_ed25519_amd_window_keep_scratch_footprint: device scratch bytes of Window.keep_dev for n items."""
+    return int(lib().fd_ed25519_amd_window_keep_scratch_footprint(int(n)))
+
+
 class EngineBusy(EngineError):
     """FD_ED25519_AMD_ERR_BUSY: every slot of the engine carries a submission."""
 
@@ -365,6 +442,7 @@ class Engine:
     def __init__(self, device=0, batch_max=1 << 16, blob_max=None, mode=MODE_REFERENCE, nslot=None):
         _check_mode(mode)
         self._h = None
+        self._window = None  # the attached Window, kept alive
         self._pending = {}   # ticket -> (outputs of the delivered submission, what must stay alive until then)
         if blob_max is None:
             blob_max = max(batch_max * 256, MSG_MAX)
@@ -387,6 +465,15 @@ class Engine:
     def mode(self):
         return int(lib().fd_ed25519_amd_mode(self._h))
 
+    def set_window(self, win):
+        """fd_ed25519_amd_set_window: the want_keep submissions filter against
+        win (a Window on this engine's device, depth >= batch_max) and feed
+        it; None detaches.  Refused while submissions are in flight."""
+        rc = lib().fd_ed25519_amd_set_window(self._h, win._h if win is not None else None)
+        if rc:
+            raise EngineError("fd_ed25519_amd_set_window rc=%d" % rc)
+        self._window = win
+
     def close(self):
         """fd_ed25519_amd_delete: waits for the submissions in flight and
         delivers none of them."""
@@ -394,6 +481,7 @@ class Engine:
             lib().fd_ed25519_amd_delete(self._h)
             self._h = None
             self._pending.clear()
+            self._window = None
 
     def __del__(self):
         try:

@@ -586,7 +586,8 @@ fd_ed25519_amd_async_wait( fd_ed25519_amd_t * eng, ulong * ticket );
    transaction family (fd_txn_amd.h).  The verdicts are those of the engine's
    mode at submit: an s-window signature is a survivor in reference mode and
    not in strict mode.  The dedup window is one submission, which is one
-   chunk.
+   chunk -- unless the engine has a window attached ("The dedup window"
+   below), which carries the tags from one submission to the next.
 
    fd_ed25519_amd_keep is the rule as pure host code (no device; what a
    CPU-only caller or a unit test computes): it returns keep_cnt and writes
@@ -628,7 +629,8 @@ fd_ed25519_amd_async_wait( fd_ed25519_amd_t * eng, ulong * ticket );
    Out of scope: the synchronous multi-chunk calls and the SoA shapes (a
    dedup window over several chunks needs the inserts of different streams
    ordered), the multi-device engine, the streaming tile (which has its own
-   dedup), the drop-in fd_ed25519_verify, and dedup across submissions. */
+   dedup) and the drop-in fd_ed25519_verify.  Dedup across submissions is
+   the window's, below. */
 ulong
 fd_ed25519_amd_keep( ulong         n,
                      schar const * err,
@@ -673,6 +675,137 @@ fd_ed25519_amd_submit_batch_registered_keep( fd_ed25519_amd_t *   eng,
                                              uint *               keep,
                                              ulong *              keep_cnt,
                                              ulong *              ticket );
+
+/* ===== The dedup window: dedup across submissions =====
+
+   A window remembers the last `depth` tags its caller published, in device
+   memory, so that the _keep submissions of an engine it is attached to drop
+   what an EARLIER submission already delivered: keep[] is then what a verify
+   tile forwards, and the caller keeps no tag cache of its own.  The
+   reference's verify and dedup tiles keep an fd_tcache for this
+   (src/tango/tcache/fd_tcache.h:372-403).
+
+   The rule, one definition for every layer.  A window has a depth D >= 1 and
+   the sequence T[0..H) of every tag it ever inserted (H a 64-bit count).  Its
+   LIVE tags at H are T[q] for max( 0, H - D ) <= q < H; they are distinct by
+   construction.  One submission of n <= D items (err[i], tag[i]) acts on the
+   window as it stands WHEN THE SUBMISSION STARTS:
+     - item i is a survivor iff err[i] == 0, and tag[i] == 0 or no j < i has
+       err[j] == 0 and tag[j] == tag[i] (the rule of "Survivors"), and tag[i]
+       is not live;
+     - afterwards the survivors with a nonzero tag are appended to T in
+       ascending i, and H grows by their number.
+   Tag 0 and failing items are never inserted.  Submissions act on the window
+   in ticket order, however they overlap on the GPU and whenever they are
+   polled.
+
+   Relation to FD_TCACHE_INSERT applied item by item.  The window is queried
+   as of the submission's start, so a tag the submission's own inserts would
+   have evicted still counts as a duplicate inside that submission: the
+   effective depth is between D and D + n - 1, and no item a depth-D tcache
+   with the same history would drop is kept.  The two are equal exactly, keep
+   lists and state, whenever no tag evicted during a submission sits on a
+   passing item of that same submission.  The item-by-item rule is not the
+   rule here because it has a serial dependency: whether item i evicts the
+   oldest tag depends on how many earlier items survived, and a GPU decides
+   all items of a batch at once.
+
+   fd_ed25519_amd_window_new: a window of `depth` tags (1 ..
+   FD_ED25519_AMD_WINDOW_DEPTH_MAX) on HIP device `device`; device < 0 makes
+   a host-only window (no HIP call).  salt is the secret of the window's
+   table, as for fd_ed25519_amd_keep_dev; 0 draws one from the OS.  No output
+   depends on it.  NULL on failure.  Device memory: 8 depth bytes of ring and
+   16 bytes for each of the table's slots, whose number is the power of two
+   >= max( 4 depth, 256 ): between 72 and 136 bytes per tag of depth, 264 MiB
+   at the largest depth.  fd_ed25519_amd_window_delete waits for the window's
+   queued work and detaches it from its engine.
+
+   fd_ed25519_amd_window_keep is the rule as pure host code on a host-only
+   window (what a CPU-only caller or a unit test computes, and the tag cache
+   a caller would otherwise keep behind a windowless engine): it returns
+   keep_cnt and writes keep[0, keep_cnt) only (keep == NULL only counts).
+   n > depth, or a device window, returns ~0UL and changes nothing.
+
+   fd_ed25519_amd_window_keep_dev is the filter alone, device-resident, with
+   fd_ed25519_amd_keep_dev's conventions and arguments (the table salt is the
+   window's): d_scratch is at least
+   fd_ed25519_amd_window_keep_scratch_footprint( n ) bytes (the filter's
+   planes, then a second flag plane and its scan: about 4.2 n bytes more).
+   The caller orders the calls on one window: the same stream, or events.
+   n == 0 writes *d_keep_cnt = 0 only and leaves the window alone.  n > depth,
+   a host-only window, or a window attached to an engine returns
+   FD_ED25519_AMD_ERR_INVAL and enqueues nothing.
+
+   fd_ed25519_amd_window_export returns cnt <= depth and writes the live tags
+   to tags[0, cnt), oldest first (tags == NULL only counts); it waits for the
+   window's queued work; ~0UL on a HIP error.  fd_ed25519_amd_window_import
+   replaces the contents with tags[0, cnt), oldest first: cnt <= depth, every
+   tag nonzero and distinct; cnt == 0 is a reset.  It waits, too, and is
+   refused (ERR_INVAL) while the window's engine has submissions in flight.
+   Together they are the clean-restart hook fd_tcache has (oldest_laddr).
+
+   fd_ed25519_amd_set_window: the engine borrows the window; NULL detaches it
+   (deleting either object detaches, too).  FD_ED25519_AMD_ERR_INVAL while
+   submissions are in flight, for a window of another device (a host-only one
+   included), for depth < the engine's batch_max, and for a window attached
+   to another engine.  fd_ed25519_amd_window: the engine's window, or NULL.
+
+   With a window attached the four _keep submit forms follow the rule above
+   instead of "Survivors" alone; the signature and the transaction forms
+   share the window (a transaction's tag is its first signature's).  In the
+   transaction forms the descriptors are packed for the window's survivors
+   only.  Every other output is unchanged.  Plain submissions, _keep forms
+   with keep == NULL and the blocking calls never touch the window; without a
+   window every call is what it was.  The window does not depend on the
+   verdict mode.  A slot's stream waits for the event the previous _keep
+   submission recorded behind its window step, ahead of its own; the verify
+   kernels ahead of that point still overlap.  After a submission ends in
+   FD_ED25519_AMD_ERR_DEVICE the window's contents are undefined until an
+   import. */
+#define FD_ED25519_AMD_WINDOW_DEPTH_MAX (1UL<<22)
+
+typedef struct fd_ed25519_amd_window_s fd_ed25519_amd_window_t;
+
+fd_ed25519_amd_window_t *
+fd_ed25519_amd_window_new( int device, ulong depth, ulong salt );
+
+void
+fd_ed25519_amd_window_delete( fd_ed25519_amd_window_t * win );
+
+ulong
+fd_ed25519_amd_window_depth( fd_ed25519_amd_window_t const * win );
+
+ulong
+fd_ed25519_amd_window_keep( fd_ed25519_amd_window_t * win,
+                            ulong                     n,
+                            schar const *             err,
+                            ulong const *             tag,
+                            uint *                    keep );
+
+ulong
+fd_ed25519_amd_window_keep_scratch_footprint( ulong n );
+
+int
+fd_ed25519_amd_window_keep_dev( fd_ed25519_amd_window_t * win,
+                                ulong                     n,
+                                schar const *             d_err,
+                                ulong const *             d_tag,
+                                uint *                    d_keep,
+                                ulong *                   d_keep_cnt,
+                                void *                    d_scratch,
+                                void *                    stream );
+
+ulong
+fd_ed25519_amd_window_export( fd_ed25519_amd_window_t * win, ulong * tags );
+
+int
+fd_ed25519_amd_window_import( fd_ed25519_amd_window_t * win, ulong const * tags, ulong cnt );
+
+int
+fd_ed25519_amd_set_window( fd_ed25519_amd_t * eng, fd_ed25519_amd_window_t * win );
+
+fd_ed25519_amd_window_t *
+fd_ed25519_amd_window( fd_ed25519_amd_t const * eng );
 
 /* Device-resident batch: every pointer is HIP device memory, already
    resident (the layout of fd_ed25519_amd_verify_soa).  Enqueues the
