@@ -29,6 +29,7 @@
 #include "../../include/fd_ed25519_amd.h"
 #include "../../include/fd_txn_amd.h"
 #include "fd_ed25519_kernels.h"
+#include "fd_ed25519_emit.h"   /* the layout arithmetic alone: no kernel is compiled here */
 
 #define HIPCHK( x ) do { hipError_t _e = (x); if( _e != hipSuccess ) {                          \
     fprintf( stderr, "fd_ed25519_amd: %s failed: %s (%s:%d)\n", #x, hipGetErrorString( _e ),     \
@@ -74,6 +75,8 @@ slot_free( slot_t * s ) {
   if( s->h_dpack) (void)hipHostFree( s->h_dpack );
   if( s->d_kpack) (void)hipFree( s->d_kpack );
   if( s->h_kpack) (void)hipHostFree( s->h_kpack );
+  if( s->d_epack) (void)hipFree( s->d_epack );
+  if( s->h_epack) (void)hipHostFree( s->h_epack );
   if( s->win_done ) (void)hipEventDestroy( s->win_done );
   if( s->stream ) (void)hipStreamDestroy( s->stream );
   if( s->done   ) (void)hipEventDestroy( s->done );
@@ -257,6 +260,25 @@ slot_alloc_keep( slot_t * s, ulong cap ) {
   return FD_ED25519_AMD_OK;
 }
 
+/* The slot's output-frame buffers, on the first submission that asks for
+   frames. */
+static int
+slot_alloc_emit( slot_t * s, ulong cap ) {
+  if( s->d_epack ) return FD_ED25519_AMD_OK;
+  ulong const off_sz = ( 8UL*(cap+1UL) + 255UL ) & ~255UL;
+  HIPCHK( hipMalloc( (void **)&s->d_epack, fd_amd_emit_layout( cap ).total ) );
+  HIPCHK( hipHostMalloc( (void **)&s->h_epack, off_sz + 4UL*cap, hipHostMallocMapped | hipHostMallocCoherent ) );
+  s->h_eoff = (ulong *)s->h_epack; s->h_esz = (uint *)(s->h_epack + off_sz);
+  HIPCHK( hipHostGetDevicePointer( &s->m_eoff, s->h_epack, 0 ) );
+  s->m_esz = (uint8_t *)s->m_eoff + off_sz;
+  return FD_ED25519_AMD_OK;
+}
+
+/* The store kernel's wave cap in the engine: its stores go to host memory
+   beside the other slots' kernels (slot_launch_gather's reason, the other
+   way round). */
+#define EMIT_WAVES (128u)
+
 /* The filter step of both launch tails, for a _keep submission: the
    survivors of the chunk's n items, from their verdicts d_err (in the
    engine's mode: behind k_strict) and tags d_tag, both on the device, into
@@ -319,12 +341,19 @@ slot_drain( slot_t * s ) {
   } else if( f.k_out && s->h_kcnt[0] > f.k_n ) {   /* the same backstop for the publish list */
     fprintf( stderr, "fd_ed25519_amd: a chunk's survivors exceed its items\n" );
     fault = true;
+  } else if( f.e_off && s->h_eoff[s->h_kcnt[0]] > f.e_cap ) {   /* and for the frames (none was stored past the extent) */
+    fprintf( stderr, "fd_ed25519_amd: a chunk's frames exceed their bound\n" );
+    fault = true;
   } else {
     for( int k=0; k<f.ncp; k++ ) memcpy( f.cp[k].dst, f.cp[k].src, f.cp[k].sz );
     if( f.k_out ) {   /* keep[0, count) and the count; nothing at or beyond keep[count] */
       ulong const cnt = s->h_kcnt[0];
       if( cnt ) memcpy( f.k_out, s->h_keep, 4UL*cnt );
       *f.k_cnt = cnt;
+      if( f.e_off ) {   /* emit_off[0 .. count] and emit_sz[0 .. count); nothing beyond them */
+        memcpy( f.e_off, s->h_eoff, 8UL*(cnt + 1UL) );
+        if( cnt ) memcpy( f.e_sz, s->h_esz, 4UL*cnt );
+      }
     }
     if( f.do_out ) {   /* chunk-relative offsets -> the batch's numbering; the bytes behind the earlier chunks' */
       ulong const base = *f.d_base, tot = s->h_doff[f.do_n];
@@ -402,11 +431,18 @@ slot_launch_sig( slot_t * s, ulong n, planes_t const & p, schar * err, ulong * t
   /* survivors: the filter reads the verdicts and the workspace's tag plane where the verify left them */
   if( s->keep_arm && slot_keep( s, n, s->d_err, (ulong const *)((uint8_t const *)s->d_ws + fd_amd_ws_layout( n ).tag), NULL, NULL ) )
     return FD_ED25519_AMD_ERR_DEVICE;
+  /* frames: behind k_keep_store, from the planes the verify kernels read and the survivors in the mapped h_keep */
+  if( s->emit_arm.out &&
+      fd_amd_launch_emit_sig( (uint32_t)n, p.pub, p.sig, p.off, p.sz, p.blob, (uint32_t const *)s->m_keep, (uint64_t const *)s->m_kcnt,
+                              (void *)s->emit_arm.dev, s->emit_arm.cap, (uint64_t *)s->m_eoff, (uint32_t *)s->m_esz, s->d_epack,
+                              EMIT_WAVES, s->stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
   if( slot_done( s ) ) return FD_ED25519_AMD_ERR_DEVICE;
   slot_deliver( s, err, s->h_err, n );
   slot_deliver( s, tag, s->h_tag, 8UL*n );
   s->fl.chk_err = n;
   s->fl.k_out = s->keep_arm; s->fl.k_cnt = s->kcnt_arm; s->fl.k_n = n;
+  s->fl.e_off = s->emit_arm.out ? s->emit_arm.off : NULL; s->fl.e_sz = s->emit_arm.sz; s->fl.e_cap = s->emit_arm.cap;
   s->busy = 1;
   return FD_ED25519_AMD_OK;
 }
@@ -467,19 +503,27 @@ slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, txn_outs_t const & o, ulo
      the transactions' first slots, gathered into a device plane (not read
      back from the mapped h_ttag); with descriptors it also leaves the masked
      footprints, and the pack below runs on those: descriptors for survivors only */
+  /* frames need the survivors' packed descriptors on the device, asked for or
+     not: the pack then runs (on the masked footprints) and k_desc_out does not */
+  bool const emit = s->emit_arm.out != NULL, pack = o.desc_off || emit;
   uint32_t const * fp = s->d_fp;
   if( s->keep_arm ) {
     if( fd_amd_launch_tag_gather( s->d_ktag, s->d_ws, (uint32_t)c, s->d_tbase, s->stream ) ||
-        slot_keep( s, c, s->d_terr, s->d_ktag, o.desc_off ? s->d_fp : NULL, o.desc_off ? s->d_fpk : NULL ) )
+        slot_keep( s, c, s->d_terr, s->d_ktag, pack ? s->d_fp : NULL, pack ? s->d_fpk : NULL ) )
       return FD_ED25519_AMD_ERR_DEVICE;
     fp = s->d_fpk;
   }
-  if( o.desc_off ) {
-    if( fd_amd_launch_txn_pack( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, fp, s->d_dbsum, s->d_doff, s->d_desc,
-                                s->desc_stage, s->stream ) ||
-        fd_amd_launch_desc_out( s->m_desc, s->d_desc, s->m_doff, s->d_doff, (uint32_t)c, s->desc_stage, desc_bound, s->stream ) )
-      return FD_ED25519_AMD_ERR_DEVICE;
-  }
+  if( pack && fd_amd_launch_txn_pack( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, fp, s->d_dbsum, s->d_doff, s->d_desc,
+                                      s->desc_stage, s->stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  if( o.desc_off &&
+      fd_amd_launch_desc_out( s->m_desc, s->d_desc, s->m_doff, s->d_doff, (uint32_t)c, s->desc_stage, desc_bound, s->stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  if( emit &&
+      fd_amd_launch_emit_txn( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, (uint64_t const *)s->d_doff, s->d_desc,
+                              (uint32_t const *)s->m_keep, (uint64_t const *)s->m_kcnt, (void *)s->emit_arm.dev, s->emit_arm.cap,
+                              (uint64_t *)s->m_eoff, (uint32_t *)s->m_esz, s->d_epack, EMIT_WAVES, s->stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
   if( slot_done( s ) ) return FD_ED25519_AMD_ERR_DEVICE;
   slot_deliver( s, o.txn_err, s->h_terr, c );
   slot_deliver( s, o.txn_tag, s->h_ttag, 8UL*c );
@@ -491,6 +535,7 @@ slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, txn_outs_t const & o, ulo
   s->fl.do_out = o.desc_off; s->fl.do_n = c;
   s->fl.d_out = o.desc; s->fl.d_cap = o.desc_cap; s->fl.d_base = o.dbase;
   s->fl.k_out = s->keep_arm; s->fl.k_cnt = s->kcnt_arm; s->fl.k_n = c;
+  s->fl.e_off = emit ? s->emit_arm.off : NULL; s->fl.e_sz = s->emit_arm.sz; s->fl.e_cap = s->emit_arm.cap;
   s->busy = 1;
   return FD_ED25519_AMD_OK;
 }
@@ -1025,17 +1070,17 @@ fd_ed25519_amd_verify_txns_tag( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const
    footprint exceeds FD_TXN_MAX_SZ (fd_txn.h:88-95). */
 extern "C" ulong
 fd_txn_amd_desc_bound( ulong payload_sz ) {
-  if( payload_sz < 134UL || payload_sz > FD_TXN_AMD_PAYLOAD_MAX ) return 0UL;
-  ulong b = 20UL + 10UL*( ( payload_sz - 134UL )/3UL );
-  return ( payload_sz <= FD_TXN_AMD_MTU && b > FD_TXN_MAX_SZ ) ? FD_TXN_MAX_SZ : b;
+  return fd_amd_desc_bound1( payload_sz );   /* fd_ed25519_emit.h: the emit bound's host code shares it */
 }
+static_assert( FD_TXN_AMD_PAYLOAD_MAX == 65535UL && FD_TXN_AMD_MTU == 1232UL && FD_TXN_MAX_SZ == 3570UL,
+               "fd_amd_desc_bound1 spells these out" );
 
 /* The first buffers a transaction chunk needs on its slot. */
 static int
 slot_alloc_txn( fd_ed25519_amd_t const * e, slot_t * s, txn_outs_t const & o ) {
   int rc = slot_alloc_aux( s, e->cap );
   if( !rc && (o.txn_tag || o.sig_tag) ) rc = slot_alloc_tag( s, e->cap );
-  if( !rc && o.desc_off ) rc = slot_alloc_desc( s, e->cap, e->blob_cap );
+  if( !rc && ( o.desc_off || s->emit_arm.out ) ) rc = slot_alloc_desc( s, e->cap, e->blob_cap );   /* frames: the packed descriptors' source */
   return rc;
 }
 
@@ -1499,16 +1544,46 @@ submit_slot( fd_ed25519_amd_t * e, int * rc ) {
    for it are allocated here, on first use. */
 #define KEEP_ARGS_BAD( keep, keep_cnt ) ( !(keep) != !(keep_cnt) )
 
+/* The emit arguments of an _emit submission, before anything else happens:
+   all four or none (none: em->out stays NULL and the call is the _keep one);
+   with keep; out 64-aligned; [out, out + out_cap) inside ONE registration of
+   fd_ed25519_amd_host_register's table, the only source of the address the
+   store kernel gets.  The capacity is checked by the callers against the sum
+   of the bound (emit_cap_ok), never against the data. */
+static int
+emit_args_check( emit_args_t * em, void * out, ulong out_cap, ulong * emit_off, uint * emit_sz, uint const * keep ) {
+  *em = emit_args_t{ NULL, 0UL, NULL, NULL, 0UL };
+  if( !out && !out_cap && !emit_off && !emit_sz ) return FD_ED25519_AMD_OK;
+  if( !out || !out_cap || !emit_off || !emit_sz || !keep || ( (uintptr_t)out & 63UL ) ) return FD_ED25519_AMD_ERR_INVAL;
+  reg_view_t view;
+  uint64_t dev;
+  if( !view.xlat( out, out_cap, &dev ) ) return FD_ED25519_AMD_ERR_INVAL;
+  *em = emit_args_t{ out, out_cap, emit_off, emit_sz, dev };
+  return FD_ED25519_AMD_OK;
+}
+
+template<typename SZ>
+static bool
+emit_cap_ok( emit_args_t const & em, ulong n, SZ const * sz, bool txn ) {
+  if( !em.out ) return true;
+  ulong need = 0UL;
+  for( ulong i=0; i<n; i++ ) need += txn ? fd_txn_amd_emit_bound( (ulong)sz[i] ) : fd_ed25519_amd_emit_bound( (ulong)sz[i] );
+  return em.cap >= need;
+}
+
 template<typename STAGE>
 static int
-submit_run( fd_ed25519_amd_t * e, slot_t * s, uint * keep, ulong * keep_cnt, ulong * ticket, STAGE stage ) {
+submit_run( fd_ed25519_amd_t * e, slot_t * s, uint * keep, ulong * keep_cnt, emit_args_t const & em, ulong * ticket, STAGE stage ) {
   if( keep ) { int rc = slot_alloc_keep( s, e->cap ); if( rc ) return engine_quiesce( e, rc ); }
+  if( em.out ) { int rc = slot_alloc_emit( s, e->cap ); if( rc ) return engine_quiesce( e, rc ); }
   s->ticket = e->ticket + 1UL;
   s->tick_arm = !e->poll_event;
   s->keep_arm = keep; s->kcnt_arm = keep_cnt; s->win_arm = keep ? e->win : NULL;
+  s->emit_arm = em;
   long c = stage();
   s->tick_arm = 0;
   s->keep_arm = NULL; s->kcnt_arm = NULL; s->win_arm = NULL;
+  s->emit_arm.out = NULL;
   if( c < 0L ) return c == (long)FD_ED25519_AMD_ERR_INVAL ? FD_ED25519_AMD_ERR_INVAL : engine_quiesce( e, (int)c );
   e->ticket = s->ticket;
   e->a_tail = (e->a_tail + 1) % e->nslot; e->a_cnt++;
@@ -1526,13 +1601,24 @@ extern "C" int
 fd_ed25519_amd_submit_batch_keep( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
                                   void const * const * sig, void const * const * pub, schar * err, ulong * tag,
                                   uint * keep, ulong * keep_cnt, ulong * ticket ) {
+  return fd_ed25519_amd_submit_batch_emit( e, n, msg, sz, sig, pub, err, tag, keep, keep_cnt, NULL, 0UL, NULL, NULL, ticket );
+}
+
+extern "C" int
+fd_ed25519_amd_submit_batch_emit( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
+                                  void const * const * sig, void const * const * pub, schar * err, ulong * tag,
+                                  uint * keep, ulong * keep_cnt, void * out, ulong out_cap, ulong * emit_off, uint * emit_sz,
+                                  ulong * ticket ) {
   if( !e || !ticket || !n || KEEP_ARGS_BAD( keep, keep_cnt ) ) return FD_ED25519_AMD_ERR_INVAL;
+  emit_args_t em;
+  if( emit_args_check( &em, out, out_cap, emit_off, emit_sz, keep ) ) return FD_ED25519_AMD_ERR_INVAL;
   int rc = batch_args_check( e, n, msg, sz, sig, pub, err );
   if( rc ) return rc;
+  if( !emit_cap_ok( em, n, sz, false ) ) return FD_ED25519_AMD_ERR_INVAL;
   slot_t * s = submit_slot( e, &rc );
   if( !s ) return rc;
   if( batch_chunk( e, n, sz ) != n ) return FD_ED25519_AMD_ERR_INVAL;   /* one chunk */
-  return submit_run( e, s, keep, keep_cnt, ticket, [&]() -> long { return stage_batch( e, s, n, msg, sz, sig, pub, err, tag ); } );
+  return submit_run( e, s, keep, keep_cnt, em, ticket, [&]() -> long { return stage_batch( e, s, n, msg, sz, sig, pub, err, tag ); } );
 }
 
 extern "C" int
@@ -1546,16 +1632,28 @@ extern "C" int
 fd_ed25519_amd_submit_batch_registered_keep( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
                                              void const * const * sig, void const * const * pub, schar * err, ulong * tag,
                                              uint * keep, ulong * keep_cnt, ulong * ticket ) {
+  return fd_ed25519_amd_submit_batch_registered_emit( e, n, msg, sz, sig, pub, err, tag, keep, keep_cnt, NULL, 0UL, NULL, NULL,
+                                                      ticket );
+}
+
+extern "C" int
+fd_ed25519_amd_submit_batch_registered_emit( fd_ed25519_amd_t * e, ulong n, void const * const * msg, ulong const * sz,
+                                             void const * const * sig, void const * const * pub, schar * err, ulong * tag,
+                                             uint * keep, ulong * keep_cnt, void * out, ulong out_cap, ulong * emit_off,
+                                             uint * emit_sz, ulong * ticket ) {
   if( !e || !ticket || !n || !msg || !sz || !sig || !pub || !err || KEEP_ARGS_BAD( keep, keep_cnt ) ) return FD_ED25519_AMD_ERR_INVAL;
+  emit_args_t em;
+  if( emit_args_check( &em, out, out_cap, emit_off, emit_sz, keep ) ) return FD_ED25519_AMD_ERR_INVAL;
   reg_view_t view;
   if( !batch_registered_check( e, view, n, msg, sz, sig, pub ) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !emit_cap_ok( em, n, sz, false ) ) return FD_ED25519_AMD_ERR_INVAL;
   int rc;
   slot_t * s = submit_slot( e, &rc );
   if( !s ) return rc;
   /* one chunk: the layout over the whole submission, into the free slot's scratch */
   if( n > e->cap || fd_ed25519_amd_gather_layout( n, sz, e->cap, e->blob_cap, slot_gather_dst( e, s ) ) != n )
     return FD_ED25519_AMD_ERR_INVAL;
-  return submit_run( e, s, keep, keep_cnt, ticket, [&]() -> long { return stage_batch_registered( e, s, view, n, msg, sz, sig, pub, err, tag ); } );
+  return submit_run( e, s, keep, keep_cnt, em, ticket, [&]() -> long { return stage_batch_registered( e, s, view, n, msg, sz, sig, pub, err, tag ); } );
 }
 
 extern "C" int
@@ -1572,10 +1670,23 @@ fd_ed25519_amd_submit_txns_keep( fd_ed25519_amd_t * e, ulong txn_cnt, uchar cons
                                  uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                                  ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
                                  uint * keep, ulong * keep_cnt, ulong * ticket ) {
+  return fd_ed25519_amd_submit_txns_emit( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, txn_tag,
+                                          sig_tag, desc_off, desc, desc_cap, keep, keep_cnt, NULL, 0UL, NULL, NULL, ticket );
+}
+
+extern "C" int
+fd_ed25519_amd_submit_txns_emit( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
+                                 uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                                 ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
+                                 uint * keep, ulong * keep_cnt, void * out, ulong out_cap, ulong * emit_off, uint * emit_sz,
+                                 ulong * ticket ) {
   if( !e || !ticket || !txn_cnt || KEEP_ARGS_BAD( keep, keep_cnt ) ) return FD_ED25519_AMD_ERR_INVAL;
+  emit_args_t em;
+  if( emit_args_check( &em, out, out_cap, emit_off, emit_sz, keep ) ) return FD_ED25519_AMD_ERR_INVAL;
   int rc = fd_amd_txn_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag,
                                   desc_off, desc, desc_cap );
   if( rc ) return rc;
+  if( !emit_cap_ok( em, txn_cnt, txn_sz, true ) ) return FD_ED25519_AMD_ERR_INVAL;
   slot_t * s = submit_slot( e, &rc );
   if( !s ) return rc;
   ulong bsz = 0, ns = 0;
@@ -1583,7 +1694,7 @@ fd_ed25519_amd_submit_txns_keep( fd_ed25519_amd_t * e, ulong txn_cnt, uchar cons
     return FD_ED25519_AMD_ERR_INVAL;   /* one chunk */
   s->a_dbase = 0UL;
   txn_outs_t o = { txn_err, sig_err, txn_tag, sig_tag, desc_off, desc, desc_cap, &s->a_dbase };
-  rc = submit_run( e, s, keep, keep_cnt, ticket, [&]() -> long { return stage_txns( e, s, txn_cnt, payload, txn_off, txn_sz, o, &ns ); } );
+  rc = submit_run( e, s, keep, keep_cnt, em, ticket, [&]() -> long { return stage_txns( e, s, txn_cnt, payload, txn_off, txn_sz, o, &ns ); } );
   /* pure host numbering: the one output a submit call writes */
   if( !rc && sig_base ) fd_ed25519_amd_txn_slots( txn_cnt, payload, txn_off, txn_sz, sig_base );
   return rc;
@@ -1602,13 +1713,26 @@ fd_ed25519_amd_submit_txns_registered_keep( fd_ed25519_amd_t * e, ulong txn_cnt,
                                             ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                                             ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
                                             uint * keep, ulong * keep_cnt, ulong * ticket ) {
+  return fd_ed25519_amd_submit_txns_registered_emit( e, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, txn_tag, sig_tag,
+                                                     desc_off, desc, desc_cap, keep, keep_cnt, NULL, 0UL, NULL, NULL, ticket );
+}
+
+extern "C" int
+fd_ed25519_amd_submit_txns_registered_emit( fd_ed25519_amd_t * e, ulong txn_cnt, void const * const * txn,
+                                            ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                                            ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
+                                            uint * keep, ulong * keep_cnt, void * out, ulong out_cap, ulong * emit_off,
+                                            uint * emit_sz, ulong * ticket ) {
   if( !e || !ticket || !txn_cnt || txn_cnt > 0xFFFFFFFFUL || KEEP_ARGS_BAD( keep, keep_cnt ) ) return FD_ED25519_AMD_ERR_INVAL;
   if( txn_cnt > e->cap ) return FD_ED25519_AMD_ERR_INVAL;   /* one chunk (and it bounds the check's scratch) */
+  emit_args_t em;
+  if( emit_args_check( &em, out, out_cap, emit_off, emit_sz, keep ) ) return FD_ED25519_AMD_ERR_INVAL;
   reg_view_t view;
   std::vector<uint> slots( txn_cnt );
   int rc = txns_registered_check( e, view, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, sig_tag, desc_off, desc,
                                   desc_cap, slots.data() );
   if( rc ) return rc;
+  if( !emit_cap_ok( em, txn_cnt, txn_sz, true ) ) return FD_ED25519_AMD_ERR_INVAL;
   slot_t * s = submit_slot( e, &rc );
   if( !s ) return rc;
   /* one chunk: the layout over the whole submission, into the free slot's scratch */
@@ -1617,7 +1741,7 @@ fd_ed25519_amd_submit_txns_registered_keep( fd_ed25519_amd_t * e, ulong txn_cnt,
     return FD_ED25519_AMD_ERR_INVAL;
   s->a_dbase = 0UL;
   txn_outs_t o = { txn_err, sig_err, txn_tag, sig_tag, desc_off, desc, desc_cap, &s->a_dbase };
-  rc = submit_run( e, s, keep, keep_cnt, ticket, [&]() -> long {
+  rc = submit_run( e, s, keep, keep_cnt, em, ticket, [&]() -> long {
     return stage_txns_registered( e, s, view, txn_cnt, txn, txn_sz, slots.data(), o, &ns );
   } );
   /* pure host numbering: the one output a submit call writes */
@@ -1735,6 +1859,48 @@ fd_ed25519_amd_keep_dev( ulong n, schar const * d_err, ulong const * d_tag, uint
     return FD_ED25519_AMD_ERR_INVAL;
   if( fd_amd_launch_keep( (uint32_t)n, (int8_t const *)d_err, (uint64_t const *)d_tag, NULL, NULL, (uint32_t *)d_keep,
                           (uint64_t *)d_keep_cnt, d_scratch, salt, (hipStream_t)stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" ulong
+fd_ed25519_amd_emit_scratch_footprint( ulong n ) {
+  return n > (ulong)FD_AMD_KEEP_MAX ? 0UL : (ulong)fd_amd_emit_layout( n ).total;
+}
+
+/* The argument check both device-resident emit forms share. */
+static bool
+emit_dev_args_ok( ulong n, void const * d_keep, void const * d_keep_cnt, void const * d_out, ulong out_cap,
+                  void const * d_emit_off, void const * d_emit_sz, void const * d_scratch ) {
+  if( n > (ulong)FD_AMD_KEEP_MAX || !d_keep_cnt || ((uintptr_t)d_keep_cnt & 7UL) || !d_emit_off || ((uintptr_t)d_emit_off & 7UL) ||
+      !d_scratch || ((uintptr_t)d_scratch & 255UL) || ( out_cap && !d_out ) || ((uintptr_t)d_out & 63UL) )
+    return false;
+  return !n || ( d_keep && !((uintptr_t)d_keep & 3UL) && d_emit_sz && !((uintptr_t)d_emit_sz & 3UL) );
+}
+
+extern "C" int
+fd_ed25519_amd_emit_dev( ulong n, uchar const * d_pub, uchar const * d_sig, uint const * d_msg_off, uint const * d_msg_sz,
+                         uchar const * d_blob, uint const * d_keep, ulong const * d_keep_cnt, void * d_out, ulong out_cap,
+                         ulong * d_emit_off, uint * d_emit_sz, void * d_scratch, void * stream ) {
+  if( !emit_dev_args_ok( n, d_keep, d_keep_cnt, d_out, out_cap, d_emit_off, d_emit_sz, d_scratch ) ||
+      ( n && ( !d_pub || !d_sig || !d_msg_off || !d_msg_sz || !d_blob ) ) )
+    return FD_ED25519_AMD_ERR_INVAL;
+  if( fd_amd_launch_emit_sig( (uint32_t)n, d_pub, d_sig, d_msg_off, d_msg_sz, d_blob, d_keep, (uint64_t const *)d_keep_cnt, d_out,
+                              out_cap, (uint64_t *)d_emit_off, d_emit_sz, d_scratch, 0u, (hipStream_t)stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" int
+fd_txn_amd_emit_dev( ulong txn_cnt, uchar const * d_payload, uint const * d_txn_off, uint const * d_txn_sz,
+                     ulong const * d_desc_off, uchar const * d_desc, uint const * d_keep, ulong const * d_keep_cnt, void * d_out,
+                     ulong out_cap, ulong * d_emit_off, uint * d_emit_sz, void * d_scratch, void * stream ) {
+  if( !emit_dev_args_ok( txn_cnt, d_keep, d_keep_cnt, d_out, out_cap, d_emit_off, d_emit_sz, d_scratch ) ||
+      ( txn_cnt && ( !d_payload || !d_txn_off || !d_txn_sz || !d_desc_off || ((uintptr_t)d_desc_off & 7UL) || !d_desc ) ) )
+    return FD_ED25519_AMD_ERR_INVAL;
+  if( fd_amd_launch_emit_txn( (uint32_t)txn_cnt, d_payload, d_txn_off, d_txn_sz, (uint64_t const *)d_desc_off, d_desc, d_keep,
+                              (uint64_t const *)d_keep_cnt, d_out, out_cap, (uint64_t *)d_emit_off, d_emit_sz, d_scratch, 0u,
+                              (hipStream_t)stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
   return FD_ED25519_AMD_OK;
 }

@@ -31,7 +31,17 @@ struct slot_flight_t {
   /* survivors (k_out NULL: not asked for): on delivery *k_cnt = h_kcnt[0],
      at most k_n, and that many entries of h_keep go to k_out */
   uint *  k_out;  ulong * k_cnt;  ulong k_n;
+  /* output frames (e_off NULL: not asked for; else k_out is set): on delivery
+     h_eoff[0 .. count] go to e_off and h_esz[0 .. count) to e_sz, count being
+     the survivors'; e_cap: the extent's capacity, which h_eoff[count] never
+     exceeds */
+  ulong * e_off;  uint * e_sz;  ulong e_cap;
 };
+
+/* The emit arguments of a submission, checked (fd_ed25519_engine.cpp,
+   emit_args_check): out == NULL: none; dev: out's device address, from the
+   registration table. */
+struct emit_args_t { void * out; ulong cap; ulong * off; uint * sz; uint64_t dev; };
 
 struct slot_t {
   /* device */
@@ -84,6 +94,17 @@ struct slot_t {
   void    * m_kcnt;  void  * m_keep;
   ulong     salt;
   uint    * keep_arm; ulong * kcnt_arm;
+  /* output frames (fd_ed25519_amd_submit_*_emit; allocated by the first
+     submission that asks for them).  d_epack, one device allocation: the emit
+     kernels' scratch (fd_amd_emit_layout( cap )).  h_epack, one mapped pinned
+     allocation the kernels write: h_eoff[cap+1] and h_esz[cap] behind it
+     (m_eoff / m_esz: their device addresses).  emit_arm: the launch under way
+     is an _emit submission (out != NULL), so the slot's launch tail adds the
+     emit step behind the filter (set and cleared by submit_run, as keep_arm). */
+  uint8_t * d_epack;
+  uint8_t * h_epack; ulong * h_eoff; uint * h_esz;
+  void    * m_eoff;  void  * m_esz;
+  emit_args_t emit_arm;
   /* the dedup window (fd_ed25519_amd_set_window): win_arm, the engine's
      window while a _keep submission is being launched (NULL: none attached),
      so the filter step runs against it; win_done, recorded behind that step

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "fd_ed25519_consts.h"
+#include "fd_ed25519_emit.h"
 
 namespace {
 
@@ -371,6 +372,106 @@ fd_ed25519_amd_keep( unsigned long n, signed char const * err, unsigned long con
     cnt++;
   }
   return cnt;
+}
+
+/* Output frames (include/fd_ed25519_amd.h, "Output frames"), as pure host
+   code: the bounds, and the rule itself for both families.  The sizes and
+   strides are fd_amd_emit_frame's, the function the kernels compile. */
+unsigned long
+fd_ed25519_amd_emit_bound( unsigned long msg_sz ) {
+  return ( 96UL + msg_sz + 127UL ) & ~127UL;
+}
+
+unsigned long
+fd_txn_amd_emit_bound( unsigned long payload_sz ) {
+  unsigned long const d = fd_amd_desc_bound1( payload_sz );
+  return d ? ( ( ( payload_sz + 15UL ) & ~15UL ) + d + 2UL + 127UL ) & ~127UL : 0UL;
+}
+
+} /* extern "C" */
+
+namespace {
+
+/* The placement of both families: size( j ) is survivor j's frame size.
+   Returns the total; with out != NULL and a total above out_cap, ~0UL and
+   nothing is written, the layout included. */
+template<typename SIZE>
+unsigned long
+emit_place( unsigned long keep_cnt, void * out, unsigned long out_cap, unsigned long * emit_off, unsigned int * emit_sz, SIZE size ) {
+  unsigned long tot = 0UL;
+  for( unsigned long j=0; j<keep_cnt; j++ ) { u32 units; (void)size( j, &units ); tot += (unsigned long)units << 7; }
+  if( out && tot > out_cap ) return ~0UL;
+  unsigned long at = 0UL;
+  for( unsigned long j=0; j<keep_cnt; j++ ) {
+    u32 units; u32 const sz = size( j, &units );
+    if( emit_off ) emit_off[j] = at;
+    if( emit_sz )  emit_sz[j]  = sz;
+    at += (unsigned long)units << 7;
+  }
+  if( emit_off ) emit_off[keep_cnt] = at;
+  return tot;
+}
+
+/* zeros from a frame's last byte to the next multiple of 16 */
+inline void
+emit_pad( u8 * frame, u32 sz ) { memset( frame + sz, 0, ( ( sz + 15u ) & ~15u ) - sz ); }
+
+} /* namespace */
+
+extern "C" {
+
+unsigned long
+fd_ed25519_amd_emit( unsigned long keep_cnt, unsigned int const * keep, void const * const * msg, unsigned long const * sz,
+                     void const * const * sig, void const * const * pub, void * out, unsigned long out_cap,
+                     unsigned long * emit_off, unsigned int * emit_sz ) {
+  auto size = [&]( unsigned long j, u32 * units ) -> u32 {
+    unsigned long const m = sz[keep[j]];
+    return fd_amd_emit_frame( 0, m > 0xFFFFFFFFUL ? 0xFFFFFFFFu : (u32)m, 0u, units );
+  };
+  unsigned long const tot = emit_place( keep_cnt, out, out_cap, emit_off, emit_sz, size );
+  if( !out || tot == ~0UL ) return tot;
+  unsigned long at = 0UL;
+  for( unsigned long j=0; j<keep_cnt; j++ ) {
+    u32 units; u32 const fsz = size( j, &units );
+    unsigned int const i = keep[j];
+    u8 * f = (u8 *)out + at;
+    if( fsz ) {
+      memcpy( f, pub[i], 32 ); memcpy( f + 32, sig[i], 64 );
+      if( sz[i] ) memcpy( f + 96, msg[i], sz[i] );
+      emit_pad( f, fsz );
+    }
+    at += (unsigned long)units << 7;
+  }
+  return tot;
+}
+
+unsigned long
+fd_txn_amd_emit( unsigned long keep_cnt, unsigned int const * keep, void const * const * txn, unsigned long const * txn_sz,
+                 unsigned long const * desc_off, unsigned char const * desc, void * out, unsigned long out_cap,
+                 unsigned long * emit_off, unsigned int * emit_sz ) {
+  auto size = [&]( unsigned long j, u32 * units ) -> u32 {
+    unsigned int const i = keep[j];
+    unsigned long const p = txn_sz[i], f = desc_off[i+1] - desc_off[i];
+    return fd_amd_emit_frame( 1, p > 0xFFFFFFFFUL ? 0xFFFFFFFFu : (u32)p, f > 0xFFFFFFFFUL ? 0xFFFFFFFFu : (u32)f, units );
+  };
+  unsigned long const tot = emit_place( keep_cnt, out, out_cap, emit_off, emit_sz, size );
+  if( !out || tot == ~0UL ) return tot;
+  unsigned long at = 0UL;
+  for( unsigned long j=0; j<keep_cnt; j++ ) {
+    u32 units; u32 const fsz = size( j, &units );
+    unsigned int const i = keep[j];
+    u8 * f = (u8 *)out + at;
+    if( fsz ) {
+      u32 const p = (u32)txn_sz[i], p16 = ( p + 15u ) & ~15u, fp = (u32)( desc_off[i+1] - desc_off[i] );
+      if( p ) memcpy( f, txn[i], p );
+      memset( f + p, 0, p16 - p );
+      if( fp ) memcpy( f + p16, desc + desc_off[i], fp );
+      f[p16 + fp] = (u8)p; f[p16 + fp + 1u] = (u8)( p >> 8 );
+      emit_pad( f, fsz );
+    }
+    at += (unsigned long)units << 7;
+  }
+  return tot;
 }
 
 /* Batch keygen + sign over the engine's SoA layout, nthread host threads:

@@ -78,6 +78,7 @@ int fd_amd_launch_txn_pack( uint32_t txn_cnt, uint8_t const * d_payload, uint32_
    64 of them summing below 2^32): d_bsum[b] = the sum of the 64-blocks before
    block b, *d_total = the sum of all; n == 0 writes *d_total = 0 only. */
 int fd_amd_launch_scan64( uint32_t n, uint32_t const * d_val, uint64_t * d_bsum, uint64_t * d_total, hipStream_t stream );
+int fd_amd_launch_bscan64( uint32_t nblk, uint64_t * d_bsum, uint64_t * d_total, hipStream_t stream );
 int fd_amd_launch_desc_out( void * d_dst_mapped, uint8_t const * d_desc, void * d_off_mapped, uint64_t const * d_desc_off,
                             uint32_t txn_cnt, uint64_t cap, uint64_t bound, hipStream_t stream );
 
@@ -278,6 +279,28 @@ int fd_amd_launch_win_rebuild( fd_amd_win_dev_t const * w, hipStream_t stream );
 int fd_amd_launch_keep_win( uint32_t n, int8_t const * d_err, uint64_t const * d_tag, uint32_t const * d_fp, uint32_t * d_fpk,
                             uint32_t * d_keep, uint64_t * d_keep_cnt, void * d_scratch, uint64_t salt,
                             fd_amd_win_dev_t const * w, hipStream_t stream );
+
+/* Output frames (fd_ed25519_emit.h): for j < cnt = min( *d_keep_cnt, n ) the
+   frame of item d_keep[j] at d_out + d_emit_off[j], d_emit_sz[j] bytes; an
+   item >= n (or one too large for a frame) has size 0.  d_emit_off[0 .. cnt]
+   and d_emit_sz[0 .. cnt) are always complete; frame j is stored only if
+   d_emit_off[j+1] <= out_cap.  d_out: 64-aligned, device or mapped host
+   memory; d_keep / d_keep_cnt / d_emit_off (8-aligned) / d_emit_sz: device or
+   mapped host memory; d_scratch: fd_amd_emit_layout( n ).total bytes of
+   device memory, 256-aligned, contents irrelevant.  The store kernel runs at
+   most `waves` waves (0: one per block of frames).  Signature form: the five
+   verify planes.  Transaction form: the payload planes and the packed
+   descriptors (d_desc_off: n + 1 entries).  n <= FD_AMD_KEEP_MAX. */
+typedef struct { size_t idx, esz, units, off, bsum, word, total; } fd_amd_emit_layout_t;
+fd_amd_emit_layout_t fd_amd_emit_layout( size_t n );
+int fd_amd_launch_emit_sig( uint32_t n, uint8_t const * d_pub, uint8_t const * d_sig, uint32_t const * d_msg_off,
+                            uint32_t const * d_msg_sz, uint8_t const * d_blob, uint32_t const * d_keep,
+                            uint64_t const * d_keep_cnt, void * d_out, uint64_t out_cap, uint64_t * d_emit_off,
+                            uint32_t * d_emit_sz, void * d_scratch, uint32_t waves, hipStream_t stream );
+int fd_amd_launch_emit_txn( uint32_t txn_cnt, uint8_t const * d_payload, uint32_t const * d_txn_off, uint32_t const * d_txn_sz,
+                            uint64_t const * d_desc_off, uint8_t const * d_desc, uint32_t const * d_keep,
+                            uint64_t const * d_keep_cnt, void * d_out, uint64_t out_cap, uint64_t * d_emit_off,
+                            uint32_t * d_emit_sz, void * d_scratch, uint32_t waves, hipStream_t stream );
 
 /* k_ticket (fd_ed25519_async.hip): one lane stores `ticket` to the 8-aligned
    word at d_word (mapped host memory) with a system-scope release store, behind

@@ -53,6 +53,7 @@
 #include "fd_ed25519_gather.h"
 #include "fd_ed25519_keep.h"
 #include "fd_ed25519_window.h"
+#include "fd_ed25519_emit.h"
 
 /* ------------------------------------------------------------------ */
 /* launch                                                               */

@@ -160,6 +160,13 @@ int
 fd_amd_launch_scan64( uint32_t n, uint32_t const * d_val, uint64_t * d_bsum, uint64_t * d_total, hipStream_t stream ) {
   u32 nblk = (u32)( ( (u64)n + TXN_PACK_BLOCK - 1UL ) / TXN_PACK_BLOCK );
   if( nblk ) hipLaunchKernelGGL( k_desc_bsum, dim3(nblk), dim3(64), 0, stream, n, d_val, (u64 *)d_bsum );
+  return fd_amd_launch_bscan64( nblk, d_bsum, d_total, stream );
+}
+
+/* The scan's second step alone, for a caller whose own kernel left the block
+   totals: d_bsum[0, nblk) becomes its exclusive prefix sum, *d_total the sum. */
+int
+fd_amd_launch_bscan64( uint32_t nblk, uint64_t * d_bsum, uint64_t * d_total, hipStream_t stream ) {
   hipLaunchKernelGGL( k_desc_bscan, dim3(1), dim3(64), 0, stream, nblk, (u64 *)d_bsum, (u64 *)d_total );
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -191,6 +191,19 @@ def lib():
            "fd_ed25519_amd_submit_batch_registered_keep": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, c_ulong_p], i),
            "fd_ed25519_amd_submit_txns_keep": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, c_ulong_p], i),
            "fd_ed25519_amd_submit_txns_registered_keep": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, c_ulong_p], i),
+           # output frames: the survivors' bytes, written by the GPU
+           "fd_ed25519_amd_emit_bound": ([ul], ul), "fd_txn_amd_emit_bound": ([ul], ul),
+           "fd_ed25519_amd_emit": ([ul, vp, vp, vp, vp, vp, vp, ul, vp, vp], ul),
+           "fd_txn_amd_emit": ([ul, vp, vp, vp, vp, vp, vp, ul, vp, vp], ul),
+           "fd_ed25519_amd_emit_scratch_footprint": ([ul], ul),
+           "fd_ed25519_amd_emit_dev": ([ul, vp, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, vp, vp], i),
+           "fd_txn_amd_emit_dev": ([ul, vp, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, vp, vp], i),
+           "fd_ed25519_amd_submit_batch_emit": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, c_ulong_p], i),
+           "fd_ed25519_amd_submit_batch_registered_emit": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, c_ulong_p], i),
+           "fd_ed25519_amd_submit_txns_emit": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, vp, ul, vp, vp,
+                                                c_ulong_p], i),
+           "fd_ed25519_amd_submit_txns_registered_emit": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, vp, ul, vp, vp,
+                                                           c_ulong_p], i),
            # the dedup window: dedup across submissions
            "fd_ed25519_amd_window_new": ([i, ul, ul], vp), "fd_ed25519_amd_window_delete": ([vp], None),
            "fd_ed25519_amd_window_depth": ([vp], ul),
@@ -322,17 +335,94 @@ def keep(err, tag):
 class _Keep:
     """The survivor outputs of one want_keep submission, alive until it is
     delivered: args() is the (keep, keep_cnt) pair of the _keep submit calls
-    (NULL, NULL when not asked for), result() keep[:keep_cnt]."""
+    (NULL, NULL when not asked for), result() keep[:keep_cnt].  With emit (a
+    registered uint8 array, the submission's extent) the call is the _emit
+    form (suffix): args() ends with out, out_cap, emit_off, emit_sz and
+    results() with the pair (emit_off[:keep_cnt + 1], emit_sz[:keep_cnt])."""
 
-    def __init__(self, n, want):
+    def __init__(self, n, want, emit=None):
+        if emit is not None:
+            if not want:
+                raise EngineError("emit= needs want_keep=True: the frames are the survivors'")
+            if emit.dtype != np.uint8 or not emit.flags["C_CONTIGUOUS"]:
+                raise EngineError("emit= takes a contiguous uint8 array")
         self.keep = np.zeros(max(n, 1), np.uint32) if want else None
         self.cnt = np.zeros(1, np.uint64) if want else None
+        self.emit = emit
+        self.eoff = np.zeros(n + 1, np.uint64) if emit is not None else None
+        self.esz = np.zeros(max(n, 1), np.uint32) if emit is not None else None
+        self.suffix = "_emit" if emit is not None else "_keep"
 
     def args(self):
-        return (_ptr(self.keep), _ptr(self.cnt)) if self.keep is not None else (None, None)
+        a = (_ptr(self.keep), _ptr(self.cnt)) if self.keep is not None else (None, None)
+        if self.emit is not None:
+            a += (ctypes.c_void_p(self.emit.ctypes.data), int(self.emit.nbytes), _ptr(self.eoff), _ptr(self.esz))
+        return a
 
     def result(self):
         return self.keep[:int(self.cnt[0])]
+
+    def results(self):
+        """What a want_keep submission appends to its delivered tuple."""
+        c = int(self.cnt[0])
+        return (self.keep[:c],) + (((self.eoff[:c + 1], self.esz[:c]),) if self.emit is not None else ())
+
+
+def emit_bound(msg_sz):
+    """fd_ed25519_amd_emit_bound: round_up(96 + msg_sz, 128), the extent a
+    signature item needs in an emit= submission (no device)."""
+    return int(lib().fd_ed25519_amd_emit_bound(int(msg_sz)))
+
+
+def txn_emit_bound(payload_sz):
+    """fd_txn_amd_emit_bound: the extent a transaction of payload_sz bytes
+    needs in an emit= submission; 0 where no payload of that size parses."""
+    return int(lib().fd_txn_amd_emit_bound(int(payload_sz)))
+
+
+def _ptr_array(items):
+    """(buffers, uint64 addresses, uint64 sizes) of a list of bytes-like."""
+    raw = [bytes(b) for b in items]
+    bufs = [ctypes.create_string_buffer(b, max(len(b), 1)) for b in raw]
+    return bufs, np.array([ctypes.addressof(b) for b in bufs], np.uint64), np.array([len(b) for b in raw], np.uint64)
+
+
+def _emit_host(fn, keep, args, n_items, out, out_cap):
+    k = np.ascontiguousarray(keep, np.uint32)
+    c = int(k.size)
+    eoff, esz = np.zeros(c + 1, np.uint64), np.zeros(max(c, 1), np.uint32)
+    cap = (int(out.nbytes) if out_cap is None else int(out_cap)) if out is not None else 0
+    assert out is None or (out.dtype == np.uint8 and cap <= out.nbytes)
+    assert not c or int(k.max()) < n_items
+    tot = int(fn(c, _ptr(k), *args, ctypes.c_void_p(out.ctypes.data) if out is not None else None, cap, _ptr(eoff), _ptr(esz)))
+    return tot, eoff, esz[:c]
+
+
+def emit(keep, msgs, sigs, pubs, out=None, out_cap=None):
+    """fd_ed25519_amd_emit: the output-frame rule of the signature family on
+    the host (no device).  For survivor j, item i = keep[j], the frame pub[i]
+    | sig[i] | msg[i] goes to out + emit_off[j] (emit_sz[j] = 96 + len(msg[i])
+    bytes, then zeros up to a multiple of 16); emit_off[j+1] = emit_off[j] +
+    round_up(emit_sz[j], 128).  out: a uint8 array or None (layout only);
+    out_cap: its capacity (default: all of it).  Returns (total, emit_off,
+    emit_sz); total is 2**64 - 1, and nothing is written, when the frames do
+    not fit.  What an emit= submission writes from the GPU."""
+    mb, mp, msz = _ptr_array(msgs)
+    sb, sp, _ = _ptr_array(sigs)
+    pb, pp, _ = _ptr_array(pubs)
+    return _emit_host(lib().fd_ed25519_amd_emit, keep, (_ptr(mp), _ptr(msz), _ptr(sp), _ptr(pp)), len(mb), out, out_cap)
+
+
+def txn_emit(keep, payloads, desc_off, desc, out=None, out_cap=None):
+    """fd_txn_amd_emit: the rule of the transaction family on the host.  The
+    frame of transaction i is payload | zeros up to round_up(P, 16) | its
+    fd_txn_t, desc[desc_off[i]:desc_off[i+1]] as the want_desc calls return
+    them | P as a little-endian u16.  Arguments and result as emit."""
+    tb, tp, tsz = _ptr_array(payloads)
+    do = np.ascontiguousarray(desc_off, np.uint64)
+    d = np.ascontiguousarray(desc, np.uint8)
+    assert do.size == len(tb) + 1 and int(do[-1]) <= d.size
+    return _emit_host(lib().fd_txn_amd_emit, keep, (_ptr(tp), _ptr(tsz), _ptr(do), _ptr(d)), len(tb), out, out_cap)
 
 
 # ---------------------------------------------------------------- batch engine
@@ -511,7 +601,8 @@ class Engine:
         self._pending[int(ticket.value)] = (finish, keep)
         return int(ticket.value)
 
-    def submit_batch_ptrs(self, pub_ptr, sig_ptr, msg_ptr, msg_sz, want_tags=False, registered=True, want_keep=False):
+    def submit_batch_ptrs(self, pub_ptr, sig_ptr, msg_ptr, msg_sz, want_tags=False, registered=True, want_keep=False,
+                          emit=None):
         """fd_ed25519_amd_submit_batch_registered (registered=False:
         fd_ed25519_amd_submit_batch, which copies the bytes behind the
         pointers before it returns): verify_batch_ptrs as one chunk, launched
@@ -520,7 +611,11 @@ class Engine:
         batch is empty or exceeds one chunk.  Registered: the bytes behind the
         pointers must stay valid until delivery.  want_keep (the _keep form of
         either call): the delivered result is a tuple that ends with keep, the
-        uint32 indices of the survivors (module function keep), ascending."""
+        uint32 indices of the survivors (module function keep), ascending.
+        emit (the _emit form, with want_keep): a uint8 array inside one
+        host_register registration, 64-aligned, at least the sum of
+        emit_bound(msg_sz) bytes; the GPU writes the survivors' frames into it
+        (module function emit) and the tuple ends with (emit_off, emit_sz)."""
         pp = np.ascontiguousarray(pub_ptr, np.uint64)
         sp = np.ascontiguousarray(sig_ptr, np.uint64)
         mp = np.ascontiguousarray(msg_ptr, np.uint64)
@@ -532,28 +627,29 @@ class Engine:
         name = "fd_ed25519_amd_submit_batch_registered" if registered else "fd_ed25519_amd_submit_batch"
         t = ctypes.c_ulong(0)
         args = (self._h, n, _ptr(mp), _ptr(sz), _ptr(sp), _ptr(pp), _ptr(err), _ptr(tags) if want_tags else None)
-        if want_keep:
-            name, k = name + "_keep", _Keep(n, True)
+        if want_keep or emit is not None:
+            k = _Keep(n, want_keep, emit)
+            name = name + k.suffix
             rc = getattr(lib(), name)(*args, *k.args(), ctypes.byref(t))
-            finish = lambda: (err[:n], tags[:n], k.result()) if want_tags else (err[:n], k.result())
+            finish = lambda: ((err[:n], tags[:n]) if want_tags else (err[:n],)) + k.results()
         else:
             rc = getattr(lib(), name)(*args, ctypes.byref(t))
             finish = lambda: (err[:n], tags[:n]) if want_tags else err[:n]
-        return self._submitted(name, rc, t, finish, (pub_ptr, sig_ptr, msg_ptr) if registered else None)
+        return self._submitted(name, rc, t, finish, ((pub_ptr, sig_ptr, msg_ptr) if registered else None, emit))
 
-    def submit_batch(self, msgs, sigs, pubs, want_tags=False, want_keep=False):
+    def submit_batch(self, msgs, sigs, pubs, want_tags=False, want_keep=False, emit=None):
         """verify_batch (lists of bytes-like) as a submission: staged, every
-        byte copied before it returns.  Returns the ticket.  want_keep: as
-        submit_batch_ptrs."""
+        byte copied before it returns.  Returns the ticket.  want_keep, emit:
+        as submit_batch_ptrs."""
         n = len(msgs)
         keep = [bytes(m) for m in msgs] + [bytes(s) for s in sigs] + [bytes(p) for p in pubs]
         bufs = [ctypes.create_string_buffer(b, max(len(b), 1)) for b in keep]
         addr = np.array([ctypes.addressof(b) for b in bufs], np.uint64)
         return self.submit_batch_ptrs(addr[2 * n:], addr[n:2 * n], addr[:n], [len(b) for b in keep[:n]],
-                                      want_tags=want_tags, registered=False, want_keep=want_keep)
+                                      want_tags=want_tags, registered=False, want_keep=want_keep, emit=emit)
 
     def submit_txns_ptrs(self, txn_ptr, txn_sz, want_sigs=False, want_tags=False, want_desc=False, registered=True,
-                         want_keep=False):
+                         want_keep=False, emit=None):
         """fd_ed25519_amd_submit_txns_registered: verify_txns_ptrs as one
         chunk, launched now and delivered by poll() / wait(); the payloads must
         stay valid until then.  registered=False: the payloads are copied here
@@ -561,7 +657,9 @@ class Engine:
         ticket.  want_keep (fd_ed25519_amd_submit_txns_registered_keep): the
         delivered tuple ends with keep, the uint32 indices of the surviving
         transactions, ascending; with want_desc the descriptors are then those
-        of the survivors only."""
+        of the survivors only.  emit (the _emit form, with want_keep): as
+        submit_batch_ptrs, at least the sum of txn_emit_bound(txn_sz) bytes;
+        the frames are module function txn_emit's."""
         tp = np.ascontiguousarray(txn_ptr, np.uint64)
         sz = np.ascontiguousarray(txn_sz, np.uint64)
         n = int(tp.size)
@@ -572,29 +670,31 @@ class Engine:
             pays = [ctypes.string_at(int(p), int(z)) if z else b"" for p, z in zip(tp.tolist(), sz.tolist())]
             off = np.concatenate(([0], np.cumsum(sz)[:-1])).astype(np.uint32) if n else np.zeros(0, np.uint32)
             return self.submit_txns(np.frombuffer(b"".join(pays), np.uint8), off, sz.astype(np.uint32),
-                                    want_sigs=want_sigs, want_tags=want_tags, want_desc=want_desc, want_keep=want_keep)
+                                    want_sigs=want_sigs, want_tags=want_tags, want_desc=want_desc, want_keep=want_keep,
+                                    emit=emit)
         base, tot = txn_slots_ptrs(tp, sz) if (want_sigs or want_tags) else (None, 0)
-        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc, want_keep)
+        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc, want_keep, emit)
         t = ctypes.c_ulong(0)
-        name = "fd_ed25519_amd_submit_txns_registered" + ("_keep" if want_keep else "")
+        name = "fd_ed25519_amd_submit_txns_registered" + o.suffix
         rc = getattr(lib(), name)(self._h, n, _ptr(tp), _ptr(sz), *o.args(), ctypes.byref(t))
-        return self._submitted(name, rc, t, o.result, txn_ptr)
+        return self._submitted(name, rc, t, o.result, (txn_ptr, emit))
 
-    def submit_txns(self, payload, txn_off, txn_sz, want_sigs=False, want_tags=False, want_desc=False, want_keep=False):
+    def submit_txns(self, payload, txn_off, txn_sz, want_sigs=False, want_tags=False, want_desc=False, want_keep=False,
+                    emit=None):
         """fd_ed25519_amd_submit_txns: verify_txns as one chunk, the payload
         bytes copied before it returns, delivered by poll() / wait().  Returns
-        the ticket.  want_keep (fd_ed25519_amd_submit_txns_keep): as
-        submit_txns_ptrs."""
+        the ticket.  want_keep (fd_ed25519_amd_submit_txns_keep), emit
+        (fd_ed25519_amd_submit_txns_emit): as submit_txns_ptrs."""
         payload = np.ascontiguousarray(payload, np.uint8)
         off = np.ascontiguousarray(txn_off, np.uint32)
         sz = np.ascontiguousarray(txn_sz, np.uint32)
         n = int(off.size)
         base, tot = txn_slots(payload, off, sz) if (want_sigs or want_tags) else (None, 0)
-        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc, want_keep)
+        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc, want_keep, emit)
         t = ctypes.c_ulong(0)
-        name = "fd_ed25519_amd_submit_txns" + ("_keep" if want_keep else "")
+        name = "fd_ed25519_amd_submit_txns" + o.suffix
         rc = getattr(lib(), name)(self._h, n, _ptr(payload), _ptr(off), _ptr(sz), int(payload.size), *o.args(), ctypes.byref(t))
-        return self._submitted(name, rc, t, o.result, None)
+        return self._submitted(name, rc, t, o.result, emit)
 
     def _collect(self, name):
         t = ctypes.c_ulong(0)
@@ -787,12 +887,15 @@ class Engine:
 class _TxnOutputs:
     """The output arrays of one transaction submission, alive until it is
     delivered: args() is the (txn_err .. desc_cap) run of the submit calls'
-    arguments (want_keep: and keep, keep_cnt of the _keep forms), result()
-    what verify_txns returns once they are filled (want_keep: and keep)."""
+    arguments (want_keep: and keep, keep_cnt of the _keep forms; emit: and
+    the four of the _emit forms), result() what verify_txns returns once they
+    are filled (want_keep: and keep; emit: and (emit_off, emit_sz)); suffix:
+    the submit call's ("", "_keep" or "_emit")."""
 
-    def __init__(self, n, txn_sz, base, tot, want_sigs, want_tags, want_desc, want_keep=False):
+    def __init__(self, n, txn_sz, base, tot, want_sigs, want_tags, want_desc, want_keep=False, emit=None):
         self.n, self.base, self.want = n, base, (want_sigs, want_tags, want_desc)
-        self.k = _Keep(n, True) if want_keep else None
+        self.k = _Keep(n, want_keep, emit) if (want_keep or emit is not None) else None
+        self.suffix = self.k.suffix if self.k else ""
         self.terr = np.zeros(max(n, 1), np.int8)
         self.serr = np.zeros(max(tot, 1), np.int8) if want_sigs else None
         self.ttag = np.zeros(max(n, 1), np.uint64) if want_tags else None
@@ -814,7 +917,7 @@ class _TxnOutputs:
         if want_desc:
             out += (self.doff, self.desc[:int(self.doff[-1])])
         if self.k:
-            out += (self.k.result(),)
+            out += self.k.results()
         return out if len(out) > 1 else out[0]
 
 
@@ -1148,6 +1251,36 @@ def keep_dev(n, d_err, d_tag, d_keep, d_keep_cnt, d_scratch, salt=0, stream=0):
     rc = lib().fd_ed25519_amd_keep_dev(int(n), d_err, d_tag, d_keep, d_keep_cnt, d_scratch, int(salt) & (2**64 - 1), stream)
     if rc:
         raise EngineError("fd_ed25519_amd_keep_dev rc=%d" % rc)
+
+
+def emit_scratch_footprint(n):
+    """fd_ed25519_amd_emit_scratch_footprint: device scratch bytes of emit_dev / txn_emit_dev for n items."""
+    return int(lib().fd_ed25519_amd_emit_scratch_footprint(int(n)))
+
+
+def emit_dev(n, d_pub, d_sig, d_off, d_sz, d_blob, d_keep, d_keep_cnt, d_out, out_cap, d_emit_off, d_emit_sz, d_scratch,
+             stream=0):
+    """fd_ed25519_amd_emit_dev: the output frames alone, device-resident --
+    for j < min(*d_keep_cnt, n) the frame of item d_keep[j] (module function
+    emit) at d_out + d_emit_off[j]; frame j is stored only if d_emit_off[j+1]
+    <= out_cap, d_emit_off[0 .. cnt] and d_emit_sz[0 .. cnt) are complete
+    either way.  The inputs are verify_dev's planes.  d_out: 64-aligned;
+    d_scratch: at least emit_scratch_footprint(n) bytes, 256-aligned, contents
+    irrelevant.  No sync."""
+    rc = lib().fd_ed25519_amd_emit_dev(int(n), d_pub, d_sig, d_off, d_sz, d_blob, d_keep, d_keep_cnt, d_out, int(out_cap),
+                                       d_emit_off, d_emit_sz, d_scratch, stream)
+    if rc:
+        raise EngineError("fd_ed25519_amd_emit_dev rc=%d" % rc)
+
+
+def txn_emit_dev(txn_cnt, d_payload, d_toff, d_tsz, d_desc_off, d_desc, d_keep, d_keep_cnt, d_out, out_cap, d_emit_off,
+                 d_emit_sz, d_scratch, stream=0):
+    """fd_txn_amd_emit_dev: emit_dev for transactions (module function
+    txn_emit); d_desc_off / d_desc are what txn_parse_packed_dev left."""
+    rc = lib().fd_txn_amd_emit_dev(int(txn_cnt), d_payload, d_toff, d_tsz, d_desc_off, d_desc, d_keep, d_keep_cnt, d_out,
+                                   int(out_cap), d_emit_off, d_emit_sz, d_scratch, stream)
+    if rc:
+        raise EngineError("fd_txn_amd_emit_dev rc=%d" % rc)
 
 
 def txn_tags_dev(txn_cnt, d_tbase, d_ws, d_txn_tag, stream=0):

@@ -676,6 +676,155 @@ fd_ed25519_amd_submit_batch_registered_keep( fd_ed25519_amd_t *   eng,
                                              ulong *              keep_cnt,
                                              ulong *              ticket );
 
+/* ===== Output frames: the survivors' bytes, written by the GPU =====
+
+   A tile that reads from an input link publishes from a dcache of its own,
+   so after a _keep submission its thread would still copy every survivor
+   into that dcache.  The _emit submissions have the GPU do it: the calling
+   thread does one fd_mcache_publish per survivor and touches no payload
+   byte.
+
+   The rule (one definition, shared by every layer).  A submission's
+   survivors are keep[0, keep_cnt), as above, window included.  For survivor
+   j, item i = keep[j], a FRAME of emit_sz[j] bytes is written at
+   out + emit_off[j]:
+   - signature family: pub[i] (32) | sig[i] (64) | msg[i] (sz[i]), so
+     emit_sz = 96 + sz[i] -- the frag layout the streaming tile takes in;
+   - transaction family (fd_txn_amd.h): payload (P = txn_sz[i]) | zero bytes
+     up to P16 = round_up( P, 16 ) | fd_txn_t (F = its footprint, even) | P
+     as a little-endian u16, so emit_sz = P16 + F + 2.  A consumer reads P
+     from the frame's last two bytes; the descriptor starts at the 16-aligned
+     offset round_up( P, 16 ), so a cast to fd_txn_t * is legal; its bytes
+     are the ones fd_txn_parse writes, that is, what the _desc calls return.
+   - placement: emit_off[0] = 0, emit_off[j+1] = emit_off[j] +
+     round_up( emit_sz[j], 128 ) -- the stride of fd_dcache_compact_next,
+     without its wrap.  emit_off has keep_cnt + 1 defined entries, the last
+     one the total.  Survivor j is published with chunk = chunk_of( out ) +
+     ( emit_off[j] >> 6 ) and sz = emit_sz[j].
+   - bytes written: exactly [ emit_off[j], emit_off[j] + round_up(
+     emit_sz[j], 16 ) ) per frame, the frame and then zeros.  No other byte of
+     out, and nothing outside it, is written.
+   Each submission gets an extent of its own from the caller; there is no
+   cursor shared between submissions and no new ordering among streams.  The
+   caller decides where its ring wraps.
+
+   Pure host code (no device): fd_ed25519_amd_emit_bound( msg_sz ) =
+   round_up( 96 + msg_sz, 128 ), at least the stride of any such frame.
+   fd_ed25519_amd_emit is the rule for the signature family over pointer
+   arrays, as the batch calls take them: it returns the total byte count and
+   writes emit_off[0, keep_cnt], emit_sz[0, keep_cnt) and the frames; out ==
+   NULL only computes the layout; a total above out_cap returns ~0UL and
+   writes nothing.  It is what a CPU-only caller runs and what the tests
+   check the GPU against.
+
+   fd_ed25519_amd_emit_dev is the step alone, device-resident, with the
+   conventions of fd_ed25519_amd_keep_dev (the caller's stream, no sync, the
+   scratch's contents irrelevant).  The inputs are the verify planes and a
+   publish list in d_keep / d_keep_cnt, so a device-resident caller chains the
+   calls it already has.  d_out: 64-aligned, device or mapped host memory;
+   d_emit_off (8-aligned, n + 1 entries) and d_emit_sz (n entries): device or
+   mapped host memory; d_scratch: fd_ed25519_amd_emit_scratch_footprint( n )
+   bytes of device memory, 256-aligned (n at most 2^30; beyond, the footprint
+   is 0 and the call FD_ED25519_AMD_ERR_INVAL).  Capacity follows
+   fd_txn_amd_parse_packed_dev's rule: frame j is stored only if
+   emit_off[j+1] <= out_cap, otherwise none of it is, and d_emit_off is
+   complete either way.  Bounded reads and writes: *d_keep_cnt is clamped to
+   n; an index >= n (or an item too large for a frame: a message above
+   2^32 - 4192 bytes) emits a frame of size 0 and reads nothing; no contents
+   of d_keep cause a read or a store out of bounds.  Writes d_emit_off[0,
+   cnt], d_emit_sz[0, cnt), the frames and the scratch, nothing else.  The
+   capacity is checked on the device before any store of a frame.
+
+   The _emit submissions take the arguments of their _keep form with out,
+   out_cap, emit_off (capacity n + 1) and emit_sz (capacity n) in front of
+   ticket.  All four NULL / 0 is exactly the _keep call: nothing more is
+   launched or allocated.  FD_ED25519_AMD_ERR_INVAL, with the effect of every
+   error return: any one of the four without the others; emit without keep;
+   out not 64-aligned; [out, out + out_cap) not inside ONE registration of
+   fd_ed25519_amd_host_register (only that table is consulted; two adjacent
+   registrations do not make one range); out_cap below the sum of the bound
+   over all items of the submission -- the capacity is decided by the bound,
+   never by the data.  The GPU writes the extent between submit and
+   delivery: the caller leaves it alone and keeps it registered until then,
+   and overlapping extents of two submissions in flight are the caller's
+   error.  emit_off[0, keep_cnt] and emit_sz[0, keep_cnt) are written by the
+   poll or wait that reports the ticket, nothing beyond them, and the frames
+   are complete by then.  After FD_ED25519_AMD_ERR_DEVICE the extent's
+   contents are unspecified, inside its bounds.  With a window attached the
+   frames are the window's survivors'; the emit step runs behind the filter,
+   outside the stretch that is serial among submissions.  The verdict mode
+   matters only through keep.  Every other output is the _keep call's.  The
+   slot's buffers are allocated by the first submission that asks.  Out of
+   scope, as for _keep: the blocking calls, the SoA shapes, the multi-device
+   engine, the streaming tile and the drop-in. */
+ulong
+fd_ed25519_amd_emit_bound( ulong msg_sz );
+
+ulong
+fd_ed25519_amd_emit( ulong                keep_cnt,
+                     uint const *         keep,
+                     void const * const * msg,
+                     ulong const *        sz,
+                     void const * const * sig,
+                     void const * const * pub,
+                     void *               out,
+                     ulong                out_cap,
+                     ulong *              emit_off,
+                     uint *               emit_sz );
+
+ulong
+fd_ed25519_amd_emit_scratch_footprint( ulong n );
+
+int
+fd_ed25519_amd_emit_dev( ulong         n,
+                         uchar const * d_pub,
+                         uchar const * d_sig,
+                         uint const *  d_msg_off,
+                         uint const *  d_msg_sz,
+                         uchar const * d_blob,
+                         uint const *  d_keep,
+                         ulong const * d_keep_cnt,
+                         void *        d_out,
+                         ulong         out_cap,
+                         ulong *       d_emit_off,
+                         uint *        d_emit_sz,
+                         void *        d_scratch,
+                         void *        stream );
+
+int
+fd_ed25519_amd_submit_batch_emit( fd_ed25519_amd_t *   eng,
+                                  ulong                n,
+                                  void const * const * msg,
+                                  ulong const *        sz,
+                                  void const * const * sig,
+                                  void const * const * pub,
+                                  schar *              err,
+                                  ulong *              tag,
+                                  uint *               keep,
+                                  ulong *              keep_cnt,
+                                  void *               out,
+                                  ulong                out_cap,
+                                  ulong *              emit_off,
+                                  uint *               emit_sz,
+                                  ulong *              ticket );
+
+int
+fd_ed25519_amd_submit_batch_registered_emit( fd_ed25519_amd_t *   eng,
+                                             ulong                n,
+                                             void const * const * msg,
+                                             ulong const *        sz,
+                                             void const * const * sig,
+                                             void const * const * pub,
+                                             schar *              err,
+                                             ulong *              tag,
+                                             uint *               keep,
+                                             ulong *              keep_cnt,
+                                             void *               out,
+                                             ulong                out_cap,
+                                             ulong *              emit_off,
+                                             uint *               emit_sz,
+                                             ulong *              ticket );
+
 /* ===== The dedup window: dedup across submissions =====
 
    A window remembers the last `depth` tags its caller published, in device

@@ -520,6 +520,106 @@ fd_ed25519_amd_submit_txns_registered_keep( fd_ed25519_amd_t *   eng,
                                             ulong *              keep_cnt,
                                             ulong *              ticket );
 
+/* Output frames of the transaction family ("Output frames" in
+   fd_ed25519_amd.h, which states the rule): survivor j's frame is payload
+   (P) | zeros up to round_up( P, 16 ) | fd_txn_t (F) | P as a little-endian
+   u16, at out + emit_off[j], emit_sz[j] = round_up( P, 16 ) + F + 2 bytes.
+   - fd_txn_amd_emit_bound( payload_sz ): 0 where fd_txn_amd_desc_bound is 0,
+     otherwise round_up( round_up( payload_sz, 16 ) + fd_txn_amd_desc_bound(
+     payload_sz ) + 2, 128 ): at least the stride of any frame of a payload
+     of that size (met with equality by the MTU payload of 355 empty
+     instructions).  Pure host code.
+   - fd_txn_amd_emit: the rule on the host, over pointer arrays; desc_off /
+     desc as the _desc calls return them (F = desc_off[i+1] - desc_off[i]).
+     Returns the total; out == NULL only computes the layout; a total above
+     out_cap returns ~0UL and writes nothing.
+   - fd_txn_amd_emit_dev: the step alone, device-resident, with
+     fd_ed25519_amd_emit_dev's conventions, capacity rule and bounds.  The
+     inputs are the payload planes and what fd_txn_amd_parse_packed_dev left
+     (d_desc_off: txn_cnt + 1 entries, 8-aligned; d_desc).  A payload above
+     FD_TXN_AMD_PAYLOAD_MAX bytes has a frame of size 0; a payload the parser
+     rejected has F = 0.
+   - The _emit submissions: the _keep forms above with out, out_cap, emit_off
+     and emit_sz in front of ticket, under the rules stated there (the bound
+     is fd_txn_amd_emit_bound).  The frames are read from the slot's device
+     copy of the payloads and from the descriptors packed on the masked
+     footprints: the pack runs when emit is asked for even with desc == NULL;
+     desc / desc_off stay independent optional outputs. */
+ulong
+fd_txn_amd_emit_bound( ulong payload_sz );
+
+ulong
+fd_txn_amd_emit( ulong                keep_cnt,
+                 uint const *         keep,
+                 void const * const * txn,
+                 ulong const *        txn_sz,
+                 ulong const *        desc_off,
+                 uchar const *        desc,
+                 void *               out,
+                 ulong                out_cap,
+                 ulong *              emit_off,
+                 uint *               emit_sz );
+
+int
+fd_txn_amd_emit_dev( ulong         txn_cnt,
+                     uchar const * d_payload,
+                     uint const *  d_txn_off,
+                     uint const *  d_txn_sz,
+                     ulong const * d_desc_off,
+                     uchar const * d_desc,
+                     uint const *  d_keep,
+                     ulong const * d_keep_cnt,
+                     void *        d_out,
+                     ulong         out_cap,
+                     ulong *       d_emit_off,
+                     uint *        d_emit_sz,
+                     void *        d_scratch,
+                     void *        stream );
+
+int
+fd_ed25519_amd_submit_txns_emit( fd_ed25519_amd_t * eng,
+                                 ulong              txn_cnt,
+                                 uchar const *      payload,
+                                 uint const *       txn_off,
+                                 uint const *       txn_sz,
+                                 ulong              payload_sz,
+                                 schar *            txn_err,
+                                 uint *             sig_base,
+                                 schar *            sig_err,
+                                 ulong *            txn_tag,
+                                 ulong *            sig_tag,
+                                 ulong *            desc_off,
+                                 uchar *            desc,
+                                 ulong              desc_cap,
+                                 uint *             keep,
+                                 ulong *            keep_cnt,
+                                 void *             out,
+                                 ulong              out_cap,
+                                 ulong *            emit_off,
+                                 uint *             emit_sz,
+                                 ulong *            ticket );
+
+int
+fd_ed25519_amd_submit_txns_registered_emit( fd_ed25519_amd_t *   eng,
+                                            ulong                txn_cnt,
+                                            void const * const * txn,
+                                            ulong const *        txn_sz,
+                                            schar *              txn_err,
+                                            uint *               sig_base,
+                                            schar *              sig_err,
+                                            ulong *              txn_tag,
+                                            ulong *              sig_tag,
+                                            ulong *              desc_off,
+                                            uchar *              desc,
+                                            ulong                desc_cap,
+                                            uint *               keep,
+                                            ulong *              keep_cnt,
+                                            void *               out,
+                                            ulong                out_cap,
+                                            ulong *              emit_off,
+                                            uint *               emit_sz,
+                                            ulong *              ticket );
+
 /* Signature-slot numbering of a pointer-array batch (pure host code, no
    device): the rule of fd_ed25519_amd_txn_slots, one payload per pointer.
    txn[t] is not looked at when txn_sz[t] is 0, and a NULL txn[t] reserves
