@@ -30,6 +30,7 @@
 #include "../../include/fd_txn_amd.h"
 #include "fd_ed25519_kernels.h"
 #include "fd_ed25519_emit.h"   /* the layout arithmetic alone: no kernel is compiled here */
+#include "fd_txn_budget.h"     /* likewise: the record's codes, for the asserts below */
 
 #define HIPCHK( x ) do { hipError_t _e = (x); if( _e != hipSuccess ) {                          \
     fprintf( stderr, "fd_ed25519_amd: %s failed: %s (%s:%d)\n", #x, hipGetErrorString( _e ),     \
@@ -77,6 +78,7 @@ slot_free( slot_t * s ) {
   if( s->h_kpack) (void)hipHostFree( s->h_kpack );
   if( s->d_epack) (void)hipFree( s->d_epack );
   if( s->h_epack) (void)hipHostFree( s->h_epack );
+  if( s->h_budget) (void)hipHostFree( s->h_budget );
   if( s->win_done ) (void)hipEventDestroy( s->win_done );
   if( s->stream ) (void)hipStreamDestroy( s->stream );
   if( s->done   ) (void)hipEventDestroy( s->done );
@@ -274,6 +276,22 @@ slot_alloc_emit( slot_t * s, ulong cap ) {
   return FD_ED25519_AMD_OK;
 }
 
+/* The slot's budget plane, on the first chunk whose caller asked for the
+   compute budget: batch_max records that k_txn_budget writes in place. */
+static int
+slot_alloc_budget( slot_t * s, ulong cap ) {
+  if( s->h_budget ) return FD_ED25519_AMD_OK;
+  HIPCHK( hipHostMalloc( (void **)&s->h_budget, sizeof(fd_txn_amd_budget_t)*cap, hipHostMallocMapped | hipHostMallocCoherent ) );
+  HIPCHK( hipHostGetDevicePointer( &s->m_budget, s->h_budget, 0 ) );
+  return FD_ED25519_AMD_OK;
+}
+
+static_assert( sizeof(fd_txn_amd_budget_t) == 24UL && alignof(fd_txn_amd_budget_t) == 8UL, "fd_amd_budget_record's three words" );
+static_assert( FD_TXN_AMD_BUDGET_OK == FD_AMD_BUDGET_OK && FD_TXN_AMD_BUDGET_INVALID == FD_AMD_BUDGET_INVALID &&
+               FD_TXN_AMD_BUDGET_NOPARSE == FD_AMD_BUDGET_NOPARSE && FD_TXN_AMD_BUDGET_FLAG_SET_CU == FD_AMD_BUDGET_F_CU &&
+               FD_TXN_AMD_BUDGET_FLAG_SET_FEE == FD_AMD_BUDGET_F_FEE && FD_TXN_AMD_BUDGET_FLAG_SET_HEAP == FD_AMD_BUDGET_F_HEAP &&
+               FD_TXN_AMD_BUDGET_FLAG_SET_TOTAL_FEE == FD_AMD_BUDGET_F_TOTAL, "fd_txn_budget.h restates these" );
+
 /* The store kernel's wave cap in the engine: its stores go to host memory
    beside the other slots' kernels (slot_launch_gather's reason, the other
    way round). */
@@ -465,10 +483,12 @@ slot_launch_packed( slot_t * s, ulong n, ulong blob_sz, schar * out, ulong * tag
 /* Where one transaction chunk's outputs go: the caller's arrays at the
    chunk's first transaction (txn_err, txn_tag, desc_off) and first signature
    slot (sig_err, sig_tag), NULL where not asked for; the whole descriptor
-   buffer, and the call's running descriptor byte base. */
+   buffer, and the call's running descriptor byte base; budget at the chunk's
+   first transaction. */
 struct txn_outs_t {
   schar * txn_err; schar * sig_err; ulong * txn_tag; ulong * sig_tag;
   ulong * desc_off; uchar * desc; ulong desc_cap; ulong * dbase;
+  fd_txn_amd_budget_t * budget;   /* the chunk's first record (NULL: not asked for) */
 };
 
 /* The kernels of a transaction chunk whose payloads and planes (d_blob,
@@ -480,11 +500,17 @@ struct txn_outs_t {
    the per-signature ones (when o.sig_tag) in h_tag; with o.desc_off the
    chunk's descriptors, packed, in h_desc and their chunk-relative offsets in
    h_doff[0..c] (desc_bound: the sum of fd_txn_amd_desc_bound over the
-   chunk). */
+   chunk); with o.budget the chunk's compute budget records in h_budget. */
 static int
 slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, txn_outs_t const & o, ulong desc_bound ) {
   if( fd_amd_launch_txn_parse( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, s->d_fp, NULL, 0, s->d_tbase,
                                s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_skip, s->stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  /* compute budget: needs the payloads and the footprints alone, so it goes
+     right behind the parse (ahead of the verify kernels and of the stretch a
+     window serialises) and writes the mapped h_budget in place, as
+     k_tag_gather does h_ttag */
+  if( o.budget && fd_amd_launch_txn_budget( (uint32_t)c, s->d_blob, s->d_toff, s->d_tsz, s->d_fp, s->m_budget, s->stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
   if( nslot && slot_verify( s, nslot, slot_planes( s ), 0, s->d_skip, NULL ) ) return FD_ED25519_AMD_ERR_DEVICE;
   /* after k_strict (same stream): a transaction's verdict is its first failing signature's code in the engine's mode */
@@ -527,6 +553,7 @@ slot_launch_txn_dev( slot_t * s, ulong c, ulong nslot, txn_outs_t const & o, ulo
   if( slot_done( s ) ) return FD_ED25519_AMD_ERR_DEVICE;
   slot_deliver( s, o.txn_err, s->h_terr, c );
   slot_deliver( s, o.txn_tag, s->h_ttag, 8UL*c );
+  slot_deliver( s, o.budget, s->h_budget, sizeof(fd_txn_amd_budget_t)*c );
   if( nslot ) {
     slot_deliver( s, o.sig_err, s->h_err, nslot );
     slot_deliver( s, o.sig_tag, s->h_tag, 8UL*nslot );
@@ -1054,8 +1081,8 @@ extern "C" int
 fd_ed25519_amd_verify_txns_tag( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
                                 uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                                 ulong * txn_tag, ulong * sig_tag ) {
-  return fd_ed25519_amd_verify_txns_desc( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err,
-                                          txn_tag, sig_tag, NULL, NULL, 0UL );
+  return fd_ed25519_amd_verify_txns_budget( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err,
+                                            txn_tag, sig_tag, NULL, NULL, 0UL, NULL );
 }
 
 /* How big a descriptor can be.  A payload that parses holds at least one
@@ -1081,6 +1108,7 @@ slot_alloc_txn( fd_ed25519_amd_t const * e, slot_t * s, txn_outs_t const & o ) {
   int rc = slot_alloc_aux( s, e->cap );
   if( !rc && (o.txn_tag || o.sig_tag) ) rc = slot_alloc_tag( s, e->cap );
   if( !rc && ( o.desc_off || s->emit_arm.out ) ) rc = slot_alloc_desc( s, e->cap, e->blob_cap );   /* frames: the packed descriptors' source */
+  if( !rc && o.budget ) rc = slot_alloc_budget( s, e->cap );
   return rc;
 }
 
@@ -1168,6 +1196,15 @@ extern "C" int
 fd_ed25519_amd_verify_txns_desc( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
                                  uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                                  ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap ) {
+  return fd_ed25519_amd_verify_txns_budget( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err,
+                                            txn_tag, sig_tag, desc_off, desc, desc_cap, NULL );
+}
+
+extern "C" int
+fd_ed25519_amd_verify_txns_budget( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
+                                   uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                                   ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
+                                   fd_txn_amd_budget_t * budget ) {
   if( SYNC_REFUSED( e ) ) return FD_ED25519_AMD_ERR_INVAL;
   int rc = fd_amd_txn_args_check( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, sig_tag,
                                   desc_off, desc, desc_cap );
@@ -1179,7 +1216,8 @@ fd_ed25519_amd_verify_txns_desc( fd_ed25519_amd_t * e, ulong txn_cnt, uchar cons
   ulong gsig = 0;
   return run_ring( e, 2, txn_cnt, [&]( slot_t * s, ulong t ) -> long {
     txn_outs_t o = { txn_err + t, sig_err ? sig_err + gsig : NULL, txn_tag ? txn_tag + t : NULL,
-                     sig_tag ? sig_tag + gsig : NULL, desc_off ? desc_off + t : NULL, desc, desc_cap, &dbase };
+                     sig_tag ? sig_tag + gsig : NULL, desc_off ? desc_off + t : NULL, desc, desc_cap, &dbase,
+                     budget ? budget + t : NULL };
     ulong ns = 0;
     long c = stage_txns( e, s, txn_cnt - t, payload, txn_off + t, txn_sz + t, o, &ns );
     gsig += ns;
@@ -1251,8 +1289,8 @@ extern "C" int
 fd_ed25519_amd_verify_txns_registered_tag( fd_ed25519_amd_t * e, ulong txn_cnt, void const * const * txn,
                                            ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                                            ulong * txn_tag, ulong * sig_tag ) {
-  return fd_ed25519_amd_verify_txns_registered_desc( e, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, txn_tag, sig_tag,
-                                                     NULL, NULL, 0UL );
+  return fd_ed25519_amd_verify_txns_registered_budget( e, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, txn_tag, sig_tag,
+                                                       NULL, NULL, 0UL, NULL );
 }
 
 /* The argument check of the registered transaction calls, after e and the
@@ -1328,6 +1366,15 @@ fd_ed25519_amd_verify_txns_registered_desc( fd_ed25519_amd_t * e, ulong txn_cnt,
                                             ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                                             ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc,
                                             ulong desc_cap ) {
+  return fd_ed25519_amd_verify_txns_registered_budget( e, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, txn_tag, sig_tag,
+                                                       desc_off, desc, desc_cap, NULL );
+}
+
+extern "C" int
+fd_ed25519_amd_verify_txns_registered_budget( fd_ed25519_amd_t * e, ulong txn_cnt, void const * const * txn,
+                                              ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                                              ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc,
+                                              ulong desc_cap, fd_txn_amd_budget_t * budget ) {
   if( SYNC_REFUSED( e ) || !e || txn_cnt > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
   reg_view_t view;
   std::vector<uint> slots( txn_cnt );
@@ -1341,7 +1388,8 @@ fd_ed25519_amd_verify_txns_registered_desc( fd_ed25519_amd_t * e, ulong txn_cnt,
   ulong dbase = 0;   /* descriptor bytes of the chunks delivered so far */
   return run_ring( e, e->nslot, txn_cnt, [&]( slot_t * s, ulong t ) -> long {
     txn_outs_t o = { txn_err + t, sig_err ? sig_err + gsig : NULL, txn_tag ? txn_tag + t : NULL,
-                     sig_tag ? sig_tag + gsig : NULL, desc_off ? desc_off + t : NULL, desc, desc_cap, &dbase };
+                     sig_tag ? sig_tag + gsig : NULL, desc_off ? desc_off + t : NULL, desc, desc_cap, &dbase,
+                     budget ? budget + t : NULL };
     ulong ns = 0;
     long c = stage_txns_registered( e, s, view, txn_cnt - t, txn + t, txn_sz + t, slots.data() + t, o, &ns );
     gsig += ns;
@@ -1426,6 +1474,17 @@ fd_txn_amd_parse_dev( ulong txn_cnt, uchar const * d_payload, uint const * d_txn
   if( d_out && (out_stride < FD_TXN_MAX_SZ || (out_stride & 1UL)) ) return FD_ED25519_AMD_ERR_INVAL;
   if( fd_amd_launch_txn_parse( (uint32_t)txn_cnt, d_payload, d_txn_off, d_txn_sz, d_footprint, d_out, out_stride,
                                NULL, NULL, NULL, NULL, NULL, NULL, (hipStream_t)stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" int
+fd_txn_amd_budget_dev( ulong txn_cnt, uchar const * d_payload, uint const * d_txn_off, uint const * d_txn_sz,
+                       uint const * d_footprint, fd_txn_amd_budget_t * d_budget, void * stream ) {
+  if( txn_cnt > 0xFFFFFFFFUL ) return FD_ED25519_AMD_ERR_INVAL;
+  if( !txn_cnt ) return FD_ED25519_AMD_OK;
+  if( !d_payload || !d_txn_off || !d_txn_sz || !d_footprint || !d_budget || ( (ulong)d_budget & 7UL ) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( fd_amd_launch_txn_budget( (uint32_t)txn_cnt, d_payload, d_txn_off, d_txn_sz, d_footprint, d_budget, (hipStream_t)stream ) )
     return FD_ED25519_AMD_ERR_DEVICE;
   return FD_ED25519_AMD_OK;
 }
@@ -1670,8 +1729,8 @@ fd_ed25519_amd_submit_txns_keep( fd_ed25519_amd_t * e, ulong txn_cnt, uchar cons
                                  uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                                  ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
                                  uint * keep, ulong * keep_cnt, ulong * ticket ) {
-  return fd_ed25519_amd_submit_txns_emit( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, txn_tag,
-                                          sig_tag, desc_off, desc, desc_cap, keep, keep_cnt, NULL, 0UL, NULL, NULL, ticket );
+  return fd_ed25519_amd_submit_txns_budget( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, txn_tag,
+                                            sig_tag, desc_off, desc, desc_cap, keep, keep_cnt, NULL, 0UL, NULL, NULL, NULL, ticket );
 }
 
 extern "C" int
@@ -1680,6 +1739,17 @@ fd_ed25519_amd_submit_txns_emit( fd_ed25519_amd_t * e, ulong txn_cnt, uchar cons
                                  ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
                                  uint * keep, ulong * keep_cnt, void * out, ulong out_cap, ulong * emit_off, uint * emit_sz,
                                  ulong * ticket ) {
+  return fd_ed25519_amd_submit_txns_budget( e, txn_cnt, payload, txn_off, txn_sz, payload_sz, txn_err, sig_base, sig_err, txn_tag,
+                                            sig_tag, desc_off, desc, desc_cap, keep, keep_cnt, out, out_cap, emit_off, emit_sz,
+                                            NULL, ticket );
+}
+
+extern "C" int
+fd_ed25519_amd_submit_txns_budget( fd_ed25519_amd_t * e, ulong txn_cnt, uchar const * payload, uint const * txn_off,
+                                   uint const * txn_sz, ulong payload_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                                   ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
+                                   uint * keep, ulong * keep_cnt, void * out, ulong out_cap, ulong * emit_off, uint * emit_sz,
+                                   fd_txn_amd_budget_t * budget, ulong * ticket ) {
   if( !e || !ticket || !txn_cnt || KEEP_ARGS_BAD( keep, keep_cnt ) ) return FD_ED25519_AMD_ERR_INVAL;
   emit_args_t em;
   if( emit_args_check( &em, out, out_cap, emit_off, emit_sz, keep ) ) return FD_ED25519_AMD_ERR_INVAL;
@@ -1693,7 +1763,7 @@ fd_ed25519_amd_submit_txns_emit( fd_ed25519_amd_t * e, ulong txn_cnt, uchar cons
   if( txns_chunk( e, txn_cnt, payload, txn_off, txn_sz, &bsz, &ns, []( ulong, uchar const *, ulong, ulong, ulong ){} ) != txn_cnt )
     return FD_ED25519_AMD_ERR_INVAL;   /* one chunk */
   s->a_dbase = 0UL;
-  txn_outs_t o = { txn_err, sig_err, txn_tag, sig_tag, desc_off, desc, desc_cap, &s->a_dbase };
+  txn_outs_t o = { txn_err, sig_err, txn_tag, sig_tag, desc_off, desc, desc_cap, &s->a_dbase, budget };
   rc = submit_run( e, s, keep, keep_cnt, em, ticket, [&]() -> long { return stage_txns( e, s, txn_cnt, payload, txn_off, txn_sz, o, &ns ); } );
   /* pure host numbering: the one output a submit call writes */
   if( !rc && sig_base ) fd_ed25519_amd_txn_slots( txn_cnt, payload, txn_off, txn_sz, sig_base );
@@ -1713,8 +1783,9 @@ fd_ed25519_amd_submit_txns_registered_keep( fd_ed25519_amd_t * e, ulong txn_cnt,
                                             ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
                                             ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
                                             uint * keep, ulong * keep_cnt, ulong * ticket ) {
-  return fd_ed25519_amd_submit_txns_registered_emit( e, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, txn_tag, sig_tag,
-                                                     desc_off, desc, desc_cap, keep, keep_cnt, NULL, 0UL, NULL, NULL, ticket );
+  return fd_ed25519_amd_submit_txns_registered_budget( e, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, txn_tag, sig_tag,
+                                                       desc_off, desc, desc_cap, keep, keep_cnt, NULL, 0UL, NULL, NULL, NULL,
+                                                       ticket );
 }
 
 extern "C" int
@@ -1723,6 +1794,17 @@ fd_ed25519_amd_submit_txns_registered_emit( fd_ed25519_amd_t * e, ulong txn_cnt,
                                             ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
                                             uint * keep, ulong * keep_cnt, void * out, ulong out_cap, ulong * emit_off,
                                             uint * emit_sz, ulong * ticket ) {
+  return fd_ed25519_amd_submit_txns_registered_budget( e, txn_cnt, txn, txn_sz, txn_err, sig_base, sig_err, txn_tag, sig_tag,
+                                                       desc_off, desc, desc_cap, keep, keep_cnt, out, out_cap, emit_off, emit_sz,
+                                                       NULL, ticket );
+}
+
+extern "C" int
+fd_ed25519_amd_submit_txns_registered_budget( fd_ed25519_amd_t * e, ulong txn_cnt, void const * const * txn,
+                                              ulong const * txn_sz, schar * txn_err, uint * sig_base, schar * sig_err,
+                                              ulong * txn_tag, ulong * sig_tag, ulong * desc_off, uchar * desc, ulong desc_cap,
+                                              uint * keep, ulong * keep_cnt, void * out, ulong out_cap, ulong * emit_off,
+                                              uint * emit_sz, fd_txn_amd_budget_t * budget, ulong * ticket ) {
   if( !e || !ticket || !txn_cnt || txn_cnt > 0xFFFFFFFFUL || KEEP_ARGS_BAD( keep, keep_cnt ) ) return FD_ED25519_AMD_ERR_INVAL;
   if( txn_cnt > e->cap ) return FD_ED25519_AMD_ERR_INVAL;   /* one chunk (and it bounds the check's scratch) */
   emit_args_t em;
@@ -1740,7 +1822,7 @@ fd_ed25519_amd_submit_txns_registered_emit( fd_ed25519_amd_t * e, ulong txn_cnt,
   if( fd_ed25519_amd_txn_gather_layout( txn_cnt, txn_sz, slots.data(), e->cap, e->blob_cap, slot_gather_dst( e, s ), &ns ) != txn_cnt )
     return FD_ED25519_AMD_ERR_INVAL;
   s->a_dbase = 0UL;
-  txn_outs_t o = { txn_err, sig_err, txn_tag, sig_tag, desc_off, desc, desc_cap, &s->a_dbase };
+  txn_outs_t o = { txn_err, sig_err, txn_tag, sig_tag, desc_off, desc, desc_cap, &s->a_dbase, budget };
   rc = submit_run( e, s, keep, keep_cnt, em, ticket, [&]() -> long {
     return stage_txns_registered( e, s, view, txn_cnt, txn, txn_sz, slots.data(), o, &ns );
   } );

@@ -10,14 +10,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/fd_ed25519_amd.h"
+#include "../../include/fd_txn_amd.h"   /* fd_txn_amd_budget_t */
 
 /* The chunk in flight on a slot: what slot_drain delivers to the caller once
    the slot's event has fired, written by the two launch tails
    (slot_launch_sig, slot_launch_txn_dev) and cleared by slot_forget alone. */
 struct slot_flight_t {
   /* verdicts and tags: the first ncp of cp[], each `sz` bytes from the slot's
-     mapped staging (h_err, h_terr, h_tag, h_ttag) to the caller's array */
-  struct { void * dst; void const * src; ulong sz; } cp[4];
+     mapped staging (h_err, h_terr, h_tag, h_ttag, h_budget) to the caller's array */
+  struct { void * dst; void const * src; ulong sz; } cp[5];
   int     ncp;
   ulong   chk_err, chk_terr;   /* verdict bytes the launch writes to h_err / h_terr (checked for FD_AMD_VERDICT_DEVICE) */
   /* descriptors (do_out NULL: not asked for): on delivery
@@ -105,6 +106,10 @@ struct slot_t {
   uint8_t * h_epack; ulong * h_eoff; uint * h_esz;
   void    * m_eoff;  void  * m_esz;
   emit_args_t emit_arm;
+  /* compute budget (the _budget calls; allocated by the first call that asks
+     for it): h_budget[cap], fd_txn_amd_budget_t records in mapped pinned
+     memory that k_txn_budget writes in place (m_budget: its device address) */
+  fd_txn_amd_budget_t * h_budget; void * m_budget;
   /* the dedup window (fd_ed25519_amd_set_window): win_arm, the engine's
      window while a _keep submission is being launched (NULL: none attached),
      so the filter step runs against it; win_done, recorded behind that step

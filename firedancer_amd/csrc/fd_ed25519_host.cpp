@@ -20,6 +20,7 @@
 
 #include "fd_ed25519_consts.h"
 #include "fd_ed25519_emit.h"
+#include "fd_txn_budget.h"   /* the rule's arithmetic alone: no kernel is compiled here */
 
 namespace {
 
@@ -472,6 +473,41 @@ fd_txn_amd_emit( unsigned long keep_cnt, unsigned int const * keep, void const *
     at += (unsigned long)units << 7;
   }
   return tot;
+}
+
+/* The compute budget rule on the host (include/fd_txn_amd.h, "Compute
+   budget"): the walk over the descriptor's instruction records, with
+   fd_txn_budget.h's step, finalize and record -- the functions k_txn_budget
+   compiles.  The descriptor is read by its byte offsets (fd_txn.h:107-139,
+   146-272): acct_addr_cnt at 8, acct_addr_off at 10, instr_cnt at 18, and
+   per 10-byte instruction record from 20 on program_id at 0, data_sz at 4,
+   data_off at 8.  out: 24 bytes, any alignment. */
+int
+fd_txn_amd_budget( unsigned char const * payload, unsigned long payload_sz, void const * txn, void * out ) {
+  auto ld16 = []( u8 const * p ) -> u32 { return (u32)p[0] | ( (u32)p[1] << 8 ); };
+  fd_amd_budget_state_t st = { 0UL, 0u, 0u, 0u, 0u, 0u };
+  u32 status = txn ? FD_AMD_BUDGET_OK : FD_AMD_BUDGET_NOPARSE, ninstr = 0u;
+  if( txn ) {
+    u8 const * d = (u8 const *)txn;
+    u32 const nacct = ld16( d + 8 ), acct_off = ld16( d + 10 );
+    ninstr = ld16( d + 18 );
+    for( u32 i=0u; i<ninstr && status == FD_AMD_BUDGET_OK; i++ ) {
+      u8 const * ix = d + 20 + 10UL*i;
+      u32 const prog = ix[0], data_sz = ld16( ix + 4 ), data_off = ld16( ix + 8 );
+      if( prog >= nacct ) continue;                     /* a lookup-table account: its address is not in the payload */
+      if( (unsigned long)acct_off + 32UL*( prog + 1UL ) > payload_sz || (unsigned long)data_off + data_sz > payload_sz ) {
+        status = FD_AMD_BUDGET_NOPARSE;                 /* not this payload's descriptor */
+        break;
+      }
+      u8 const * a = payload + acct_off + 32UL*prog;
+      if( !fd_amd_budget_id_head( a ) || !fd_amd_budget_id_tail( a ) ) continue;
+      if( !fd_amd_budget_step( &st, payload + data_off, data_sz ) ) status = FD_AMD_BUDGET_INVALID;
+    }
+  }
+  uint64_t w[3];
+  fd_amd_budget_record( w, &st, ninstr, status );
+  memcpy( out, w, 24 );
+  return (int)status;
 }
 
 /* Batch keygen + sign over the engine's SoA layout, nthread host threads:

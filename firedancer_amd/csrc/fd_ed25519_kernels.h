@@ -57,6 +57,12 @@ int fd_amd_launch_txn_parse( uint32_t txn_cnt, uint8_t const * d_payload, uint32
 int fd_amd_launch_txn_reduce( uint32_t txn_cnt, uint32_t const * d_fp, uint32_t const * d_tbase,
                               int8_t const * d_err, int8_t * d_terr, hipStream_t stream );
 
+/* Compute budget (fd_txn_budget.h: k_txn_budget), after a k_txn_parse that
+   left d_fp: d_budget[t], a 24-byte fd_txn_amd_budget_t, for every
+   t < txn_cnt (device or mapped host memory, 8-aligned), and nothing else. */
+int fd_amd_launch_txn_budget( uint32_t txn_cnt, uint8_t const * d_payload, uint32_t const * d_toff, uint32_t const * d_tsz,
+                              uint32_t const * d_fp, void * d_budget, hipStream_t stream );
+
 /* Packed descriptors (fd_txn_kernels.hip), after a k_txn_parse that left
    d_fp: d_desc_off[0 .. txn_cnt] = the 64-bit exclusive prefix sum of d_fp
    (d_desc_off[txn_cnt] the total) and, for every t with d_fp[t] != 0 and

@@ -18,6 +18,7 @@
  *                 footprints and a second walk of the accepted payloads
  *                 that stores each descriptor at its offset
  *   k_desc_out    a chunk's offsets and packed bytes to mapped host memory
+ *   k_txn_budget  (fd_txn_budget.h) per transaction its compute budget and fee
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,6 +31,7 @@ typedef uint64_t u64;
 typedef int8_t   i8;
 
 #include "fd_txn_dev.h"
+#include "fd_txn_budget.h"   /* k_txn_budget: compiled here, behind fd_txn_dev.h */
 
 using namespace fd_txn_dev;
 

@@ -204,6 +204,15 @@ def lib():
                                                 c_ulong_p], i),
            "fd_ed25519_amd_submit_txns_registered_emit": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, vp, ul, vp, vp,
                                                            c_ulong_p], i),
+           # compute budget: per transaction its compute units and fee
+           "fd_txn_amd_budget": ([vp, ul, vp, vp], i),
+           "fd_txn_amd_budget_dev": ([ul, vp, vp, vp, vp, vp, vp], i),
+           "fd_ed25519_amd_verify_txns_budget": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp, vp, vp, ul, vp], i),
+           "fd_ed25519_amd_verify_txns_registered_budget": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, ul, vp], i),
+           "fd_ed25519_amd_submit_txns_budget": ([vp, ul, vp, vp, vp, ul, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, vp, ul, vp, vp,
+                                                  vp, c_ulong_p], i),
+           "fd_ed25519_amd_submit_txns_registered_budget": ([vp, ul, vp, vp, vp, vp, vp, vp, vp, vp, vp, ul, vp, vp, vp, ul, vp, vp,
+                                                             vp, c_ulong_p], i),
            # the dedup window: dedup across submissions
            "fd_ed25519_amd_window_new": ([i, ul, ul], vp), "fd_ed25519_amd_window_delete": ([vp], None),
            "fd_ed25519_amd_window_depth": ([vp], ul),
@@ -649,7 +658,7 @@ class Engine:
                                       want_tags=want_tags, registered=False, want_keep=want_keep, emit=emit)
 
     def submit_txns_ptrs(self, txn_ptr, txn_sz, want_sigs=False, want_tags=False, want_desc=False, registered=True,
-                         want_keep=False, emit=None):
+                         want_keep=False, emit=None, want_budget=False):
         """fd_ed25519_amd_submit_txns_registered: verify_txns_ptrs as one
         chunk, launched now and delivered by poll() / wait(); the payloads must
         stay valid until then.  registered=False: the payloads are copied here
@@ -659,7 +668,9 @@ class Engine:
         transactions, ascending; with want_desc the descriptors are then those
         of the survivors only.  emit (the _emit form, with want_keep): as
         submit_batch_ptrs, at least the sum of txn_emit_bound(txn_sz) bytes;
-        the frames are module function txn_emit's."""
+        the frames are module function txn_emit's.  want_budget (the _budget
+        form): the delivered tuple ends with the BUDGET_DTYPE records of all
+        the transactions (module function txn_budget), behind everything else."""
         tp = np.ascontiguousarray(txn_ptr, np.uint64)
         sz = np.ascontiguousarray(txn_sz, np.uint64)
         n = int(tp.size)
@@ -671,26 +682,27 @@ class Engine:
             off = np.concatenate(([0], np.cumsum(sz)[:-1])).astype(np.uint32) if n else np.zeros(0, np.uint32)
             return self.submit_txns(np.frombuffer(b"".join(pays), np.uint8), off, sz.astype(np.uint32),
                                     want_sigs=want_sigs, want_tags=want_tags, want_desc=want_desc, want_keep=want_keep,
-                                    emit=emit)
+                                    emit=emit, want_budget=want_budget)
         base, tot = txn_slots_ptrs(tp, sz) if (want_sigs or want_tags) else (None, 0)
-        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc, want_keep, emit)
+        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc, want_keep, emit, want_budget)
         t = ctypes.c_ulong(0)
         name = "fd_ed25519_amd_submit_txns_registered" + o.suffix
         rc = getattr(lib(), name)(self._h, n, _ptr(tp), _ptr(sz), *o.args(), ctypes.byref(t))
         return self._submitted(name, rc, t, o.result, (txn_ptr, emit))
 
     def submit_txns(self, payload, txn_off, txn_sz, want_sigs=False, want_tags=False, want_desc=False, want_keep=False,
-                    emit=None):
+                    emit=None, want_budget=False):
         """fd_ed25519_amd_submit_txns: verify_txns as one chunk, the payload
         bytes copied before it returns, delivered by poll() / wait().  Returns
         the ticket.  want_keep (fd_ed25519_amd_submit_txns_keep), emit
-        (fd_ed25519_amd_submit_txns_emit): as submit_txns_ptrs."""
+        (fd_ed25519_amd_submit_txns_emit), want_budget
+        (fd_ed25519_amd_submit_txns_budget): as submit_txns_ptrs."""
         payload = np.ascontiguousarray(payload, np.uint8)
         off = np.ascontiguousarray(txn_off, np.uint32)
         sz = np.ascontiguousarray(txn_sz, np.uint32)
         n = int(off.size)
         base, tot = txn_slots(payload, off, sz) if (want_sigs or want_tags) else (None, 0)
-        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc, want_keep, emit)
+        o = _TxnOutputs(n, sz, base, tot, want_sigs, want_tags, want_desc, want_keep, emit, want_budget)
         t = ctypes.c_ulong(0)
         name = "fd_ed25519_amd_submit_txns" + o.suffix
         rc = getattr(lib(), name)(self._h, n, _ptr(payload), _ptr(off), _ptr(sz), int(payload.size), *o.args(), ctypes.byref(t))
@@ -817,7 +829,7 @@ class Engine:
         return self.verify_batch_ptrs(base + np.asarray(pub_off, np.uint64), base + np.asarray(sig_off, np.uint64),
                                       base + np.asarray(msg_off, np.uint64), msg_sz, want_tags=want_tags)
 
-    def verify_txns(self, payload, txn_off, txn_sz, want_sigs=False, want_tags=False, want_desc=False):
+    def verify_txns(self, payload, txn_off, txn_sz, want_sigs=False, want_tags=False, want_desc=False, want_budget=False):
         """Wire-format transaction batch (include/fd_txn_amd.h): parse on the
         GPU, verify every signature (multi-signer rule), one verdict per
         transaction in {0, -1, -2, -3, FD_TXN_AMD_ERR_PARSE}.  With
@@ -828,16 +840,20 @@ class Engine:
         want_desc (fd_ed25519_amd_verify_txns_desc) the tuple ends with
         (desc_off, desc): uint64[n+1] offsets and the uint8[desc_off[-1]]
         packed fd_txn_t descriptors of the transactions that parse; the
-        buffer is sized with txn_desc_bound."""
-        return _verify_txns("fd_ed25519_amd_verify_txns", self._h, payload, txn_off, txn_sz, want_sigs, want_tags, want_desc)
+        buffer is sized with txn_desc_bound.  With want_budget
+        (fd_ed25519_amd_verify_txns_budget) the tuple ends with the
+        BUDGET_DTYPE records of all the transactions (txn_budget)."""
+        return _verify_txns("fd_ed25519_amd_verify_txns", self._h, payload, txn_off, txn_sz, want_sigs, want_tags, want_desc,
+                            want_budget)
 
-    def verify_txns_ptrs(self, txn_ptr, txn_sz, want_sigs=False, want_tags=False, want_desc=False):
+    def verify_txns_ptrs(self, txn_ptr, txn_sz, want_sigs=False, want_tags=False, want_desc=False, want_budget=False):
         """fd_ed25519_amd_verify_txns_registered: the transaction batch in
         pointer-array form with no host staging.  txn_ptr: uint64 array of
         host addresses (txn_sz[t] payload bytes behind each, any alignment),
         every non-empty range inside one host_register registration; the GPU
         fetches the payloads itself.  Returns what verify_txns returns for
-        the same payloads (want_desc: fd_ed25519_amd_verify_txns_registered_desc)."""
+        the same payloads (want_desc: fd_ed25519_amd_verify_txns_registered_desc;
+        want_budget: fd_ed25519_amd_verify_txns_registered_budget)."""
         tp = np.ascontiguousarray(txn_ptr, np.uint64)
         sz = np.ascontiguousarray(txn_sz, np.uint64)
         n = int(tp.size)
@@ -855,8 +871,17 @@ class Engine:
         ttag = stag = None
         if want_tags:
             ttag, stag = np.zeros(max(n, 1), np.uint64), np.zeros(max(tot, 1), np.uint64)
+        doff = desc = None
         if want_desc:
             doff, desc = _desc_buffers(sz)
+        if want_budget:
+            budget = np.zeros(max(n, 1), BUDGET_DTYPE)
+            rc = lib().fd_ed25519_amd_verify_txns_registered_budget(*args, _ptr(ttag) if want_tags else None,
+                                                                    _ptr(stag) if want_tags else None,
+                                                                    _ptr(doff) if want_desc else None,
+                                                                    _ptr(desc) if want_desc else None,
+                                                                    int(desc.size) if want_desc else 0, _ptr(budget))
+        elif want_desc:
             rc = lib().fd_ed25519_amd_verify_txns_registered_desc(*args, _ptr(ttag) if want_tags else None,
                                                                   _ptr(stag) if want_tags else None, _ptr(doff), _ptr(desc),
                                                                   int(desc.size))
@@ -873,15 +898,18 @@ class Engine:
             out += (ttag[:n], stag[:int(base[-1])])
         if want_desc:
             out += (doff, desc[:int(doff[-1])])
+        if want_budget:
+            out += (budget[:n],)
         return out if len(out) > 1 else out[0]
 
-    def verify_txns_registered(self, arena, txn_off, txn_sz, want_sigs=False, want_tags=False, want_desc=False):
+    def verify_txns_registered(self, arena, txn_off, txn_sz, want_sigs=False, want_tags=False, want_desc=False,
+                               want_budget=False):
         """verify_txns_ptrs over one registered uint8 arena (host_register):
         transaction t is arena[txn_off[t] : + txn_sz[t]]."""
         assert arena.dtype == np.uint8 and arena.flags["C_CONTIGUOUS"]
         base = np.uint64(arena.ctypes.data)
         return self.verify_txns_ptrs(base + np.asarray(txn_off, np.uint64), txn_sz, want_sigs=want_sigs,
-                                     want_tags=want_tags, want_desc=want_desc)
+                                     want_tags=want_tags, want_desc=want_desc, want_budget=want_budget)
 
 
 class _TxnOutputs:
@@ -890,12 +918,15 @@ class _TxnOutputs:
     arguments (want_keep: and keep, keep_cnt of the _keep forms; emit: and
     the four of the _emit forms), result() what verify_txns returns once they
     are filled (want_keep: and keep; emit: and (emit_off, emit_sz)); suffix:
-    the submit call's ("", "_keep" or "_emit")."""
+    the submit call's ("", "_keep", "_emit" or "_budget").  want_budget: the
+    _budget form, whose arguments are the _emit form's and the record array,
+    which result() appends behind everything else."""
 
-    def __init__(self, n, txn_sz, base, tot, want_sigs, want_tags, want_desc, want_keep=False, emit=None):
+    def __init__(self, n, txn_sz, base, tot, want_sigs, want_tags, want_desc, want_keep=False, emit=None, want_budget=False):
         self.n, self.base, self.want = n, base, (want_sigs, want_tags, want_desc)
         self.k = _Keep(n, want_keep, emit) if (want_keep or emit is not None) else None
-        self.suffix = self.k.suffix if self.k else ""
+        self.suffix = "_budget" if want_budget else (self.k.suffix if self.k else "")
+        self.budget = np.zeros(max(n, 1), BUDGET_DTYPE) if want_budget else None
         self.terr = np.zeros(max(n, 1), np.int8)
         self.serr = np.zeros(max(tot, 1), np.int8) if want_sigs else None
         self.ttag = np.zeros(max(n, 1), np.uint64) if want_tags else None
@@ -905,7 +936,14 @@ class _TxnOutputs:
     def args(self):
         p = lambda a: _ptr(a) if a is not None else None
         return (p(self.terr), p(self.base), p(self.serr), p(self.ttag), p(self.stag), p(self.doff), p(self.desc),
-                int(self.desc.size) if self.desc is not None else 0) + (self.k.args() if self.k else ())
+                int(self.desc.size) if self.desc is not None else 0) + self._tail()
+
+    def _tail(self):
+        if self.budget is None:
+            return self.k.args() if self.k else ()
+        k = self.k.args() if self.k else (None, None)              # keep, keep_cnt
+        k += (None, 0, None, None) if len(k) == 2 else ()          # out, out_cap, emit_off, emit_sz
+        return k + (_ptr(self.budget),)
 
     def result(self):
         want_sigs, want_tags, want_desc = self.want
@@ -918,7 +956,37 @@ class _TxnOutputs:
             out += (self.doff, self.desc[:int(self.doff[-1])])
         if self.k:
             out += self.k.results()
+        if self.budget is not None:
+            out += (self.budget[:self.n],)
         return out if len(out) > 1 else out[0]
+
+
+# fd_txn_amd_budget_t (include/fd_txn_amd.h, "Compute budget"): 24 bytes, little endian
+BUDGET_DTYPE = np.dtype([("rewards", "<u8"), ("compute", "<u4"), ("heap_sz", "<u4"), ("flags", "<u2"),
+                         ("cb_instr_cnt", "<u2"), ("status", "<u4")])
+BUDGET_OK, BUDGET_INVALID, BUDGET_NOPARSE = 0, 1, 2
+
+
+def txn_budget(payload, desc):
+    """fd_txn_amd_budget: the compute budget rule on the host (no device) for
+    one payload and its fd_txn_t descriptor bytes as fd_txn_parse or the
+    _desc calls return them (None or empty: the payload did not parse).
+    Returns a BUDGET_DTYPE scalar."""
+    p = np.frombuffer(bytes(payload), np.uint8)
+    d = np.frombuffer(bytes(desc), np.uint8) if desc is not None and len(desc) else None
+    out = np.zeros(1, BUDGET_DTYPE)
+    lib().fd_txn_amd_budget(_ptr(p), int(p.size), _ptr(d) if d is not None else None, _ptr(out))
+    return out[0]
+
+
+def txn_budget_dev(txn_cnt, d_payload, d_toff, d_tsz, d_fp, d_budget, stream=0):
+    """fd_txn_amd_budget_dev: the compute budget records alone,
+    device-resident, from the payload planes and the footprint plane
+    txn_parse_dev left; d_budget: 24 * txn_cnt bytes, 8-aligned.  Enqueued on
+    `stream`, no sync."""
+    rc = lib().fd_txn_amd_budget_dev(int(txn_cnt), d_payload, d_toff, d_tsz, d_fp, d_budget, stream)
+    if rc:
+        raise EngineError("fd_txn_amd_budget_dev rc=%d" % rc)
 
 
 def txn_desc_bound(sz):
@@ -991,9 +1059,10 @@ def txn_slots(payload, txn_off, txn_sz):
     return base, int(tot)
 
 
-def _verify_txns(name, h, payload, txn_off, txn_sz, want_sigs, want_tags=False, want_desc=False):
+def _verify_txns(name, h, payload, txn_off, txn_sz, want_sigs, want_tags=False, want_desc=False, want_budget=False):
     """name: fd_ed25519_amd_verify_txns or the multi form; want_tags calls its
-    _tag form, want_desc its _desc form (the single-device call only)."""
+    _tag form, want_desc its _desc form, want_budget its _budget form (the
+    last two: the single-device call only)."""
     payload = np.ascontiguousarray(payload, np.uint8)
     off = np.ascontiguousarray(txn_off, np.uint32)
     sz = np.ascontiguousarray(txn_sz, np.uint32)
@@ -1011,8 +1080,15 @@ def _verify_txns(name, h, payload, txn_off, txn_sz, want_sigs, want_tags=False, 
     ttag = stag = None
     if want_tags:
         ttag, stag = np.zeros(max(n, 1), np.uint64), np.zeros(max(tot, 1), np.uint64)
+    doff = desc = None
     if want_desc:
         doff, desc = _desc_buffers(sz)
+    if want_budget:
+        budget = np.zeros(max(n, 1), BUDGET_DTYPE)
+        rc = getattr(lib(), name + "_budget")(*args, _ptr(ttag) if want_tags else None, _ptr(stag) if want_tags else None,
+                                              _ptr(doff) if want_desc else None, _ptr(desc) if want_desc else None,
+                                              int(desc.size) if want_desc else 0, _ptr(budget))
+    elif want_desc:
         rc = getattr(lib(), name + "_desc")(*args, _ptr(ttag) if want_tags else None, _ptr(stag) if want_tags else None,
                                             _ptr(doff), _ptr(desc), int(desc.size))
     elif want_tags:
@@ -1028,6 +1104,8 @@ def _verify_txns(name, h, payload, txn_off, txn_sz, want_sigs, want_tags=False, 
         out += (ttag[:n], stag[:int(base[-1])])
     if want_desc:
         out += (doff, desc[:int(doff[-1])])
+    if want_budget:
+        out += (budget[:n],)
     return out if len(out) > 1 else out[0]
 
 

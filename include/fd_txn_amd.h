@@ -620,6 +620,208 @@ fd_ed25519_amd_submit_txns_registered_emit( fd_ed25519_amd_t *   eng,
                                             uint *               emit_sz,
                                             ulong *              ticket );
 
+/* ===== Compute budget =====
+
+   Per transaction, the two numbers pack (or any scheduler) needs first: how
+   many compute units it may burn and what it pays on top of the signature
+   fee -- what the reference's fd_compute_budget_program_init / _parse /
+   _finalize (src/ballet/pack/fd_compute_budget_program.h:71-204) make of the
+   instructions addressed to ComputeBudget111111111111111111111111111111 --
+   from the GPU, which holds the payload already, so that the consumer need
+   not walk every instruction's program address and data again.
+
+   The record of transaction t, payload p of sz bytes, descriptor d as
+   fd_txn_parse writes it.  24 bytes, 8-aligned, little endian:
+     rewards       *out_rewards of fd_compute_budget_program_finalize
+     compute       *out_compute
+     heap_sz       the state's heap_size
+     flags         the state's flags, FD_TXN_AMD_BUDGET_FLAG_* (the
+                   reference's bit values; it #undefs its own macros)
+     cb_instr_cnt  the state's compute_budget_instr_cnt
+     status        FD_TXN_AMD_BUDGET_OK, _INVALID or _NOPARSE
+
+   _NOPARSE iff the transaction has no descriptor: footprint 0, or wherever
+   the calling entry point reports FD_TXN_AMD_ERR_PARSE (the registered
+   calls' fail-closed rejection included).  Every other field is 0.
+
+   Otherwise instr[0 .. instr_cnt) are walked in order from a zeroed state.
+   Instruction i is a compute-budget instruction iff instr[i].program_id <
+   acct_addr_cnt and the 32 bytes at p + acct_addr_off + 32*program_id equal
+   the id.  The bound on program_id is ours, and deliberate: fd_txn_parse
+   (fd_txn_parse.c:200) lets program_id reach into the lookup-table accounts,
+   whose addresses are not in the payload, and comparing whatever bytes follow
+   the address array (with program_id == acct_addr_cnt, the recent blockhash)
+   would let those bytes pose as the program.  Such an instruction is never a
+   compute-budget instruction here.  Each match runs
+   fd_compute_budget_program_parse on p[data_off, +data_sz), exactly: data_sz
+   < 5 is rejected before the discriminant is looked at; then the per-kind
+   sizes (9, 5, 5, 9 for discriminants 0 to 3, no other discriminant), the
+   duplicate rules (RequestUnitsDeprecated counts as both a limit and a
+   price) and the 1024 granularity of the heap.
+
+   _INVALID: the first instruction it rejects ends the walk, and every other
+   field is 0 (the reference has written heap_size by the time the
+   granularity check fails; that partial state does not leak).
+
+   _OK otherwise, with fd_compute_budget_program_finalize( state, instr_cnt ):
+   without a limit set, cu_limit = (instr_cnt - cb_instr_cnt) * 200000 as a
+   64-bit value; compute is its low 32 bits and the fee arithmetic uses all
+   64 (they differ from 21475 non-budget instructions up, which only payloads
+   above the MTU reach).  With FLAG_SET_TOTAL_FEE rewards is total_fee,
+   otherwise min( 2^64 - 1, ceil( cu_limit * micro_lamports_per_cu / 10^6 ) ),
+   computed in the reference's split form without 128-bit arithmetic.
+
+   Verdicts, the verdict mode, keep and the window play no part: a record is
+   defined for every transaction, as a descriptor is, and a caller that
+   publishes keep[j] reads budget[keep[j]].  Whether an _INVALID transaction
+   is forwarded stays the caller's decision.
+
+   - fd_txn_amd_budget: the rule on the host, over one payload and its
+     descriptor (txn == NULL: _NOPARSE).  Makes no device call.  The
+     descriptor is trusted as fd_txn_parse's for this payload, but an address
+     or a data range of it that ends beyond payload_sz gives _NOPARSE rather
+     than a read outside the payload.  Returns the status.
+   - fd_txn_amd_budget_dev: the step alone, device-resident, with the
+     conventions of the other _dev calls: the caller's stream, no sync,
+     payloads up to 65535 B as fd_txn_amd_parse_dev takes them.  The inputs
+     are the payload planes and the footprint plane fd_txn_amd_parse_dev left
+     (0: _NOPARSE).  One lane per transaction walks the payload under a
+     checked cursor: no contents of the inputs cause a read outside
+     [d_payload + d_txn_off[t], + d_txn_sz[t]), and a bound that fails -- it
+     cannot after a genuine parse -- ends in _NOPARSE.  d_budget: 8-aligned
+     device or mapped host memory, prior contents irrelevant; d_budget[t] is
+     written for every t < txn_cnt and nothing else is.  txn_cnt == 0
+     launches nothing.
+   - The four engine calls: fd_ed25519_amd_verify_txns_desc, its registered
+     form and the two _emit submissions, each with fd_txn_amd_budget_t *
+     budget (capacity txn_cnt, plain caller memory), in front of ticket where
+     there is one.  budget == NULL is exactly the call it extends: nothing
+     more is allocated, launched or copied, and the existing functions are
+     these with NULL.  Otherwise one more kernel goes on the slot's stream
+     right behind k_txn_parse -- ahead of the verify kernels, outside the
+     stretch a dedup window serialises among submissions -- and writes the
+     chunk's records into the slot's budget plane (24 * batch_max bytes of
+     mapped pinned memory, allocated by the first call that asks); they reach
+     budget the way txn_tag does: per chunk in the blocking calls, at
+     delivery by the reporting fd_ed25519_amd_async_poll / _wait in the
+     submissions, for all txn_cnt transactions, survivors or not.  Every rule
+     of "Asynchronous submissions" holds: error returns, BUSY and an
+     undelivered submission leave budget untouched.  Every other output is
+     byte for byte that of the same call without budget.
+   Out of scope, as for descriptors: the multi-device forms, the streaming
+   tile, the drop-in call, and any change to the emit frame. */
+#define FD_TXN_AMD_BUDGET_OK      (0U)
+#define FD_TXN_AMD_BUDGET_INVALID (1U)
+#define FD_TXN_AMD_BUDGET_NOPARSE (2U)
+
+#define FD_TXN_AMD_BUDGET_FLAG_SET_CU        ((ushort)0x01)   /* fd_compute_budget_program.h:29-32 */
+#define FD_TXN_AMD_BUDGET_FLAG_SET_FEE       ((ushort)0x02)
+#define FD_TXN_AMD_BUDGET_FLAG_SET_HEAP      ((ushort)0x04)
+#define FD_TXN_AMD_BUDGET_FLAG_SET_TOTAL_FEE ((ushort)0x08)
+
+struct fd_txn_amd_budget {
+  ulong  rewards;
+  uint   compute;
+  uint   heap_sz;
+  ushort flags;
+  ushort cb_instr_cnt;
+  uint   status;
+};
+typedef struct fd_txn_amd_budget fd_txn_amd_budget_t;
+
+int
+fd_txn_amd_budget( uchar const *         payload,
+                   ulong                 payload_sz,
+                   fd_txn_t const *      txn,
+                   fd_txn_amd_budget_t * out );
+
+int
+fd_txn_amd_budget_dev( ulong                 txn_cnt,
+                       uchar const *         d_payload,
+                       uint const *          d_txn_off,
+                       uint const *          d_txn_sz,
+                       uint const *          d_footprint,
+                       fd_txn_amd_budget_t * d_budget,
+                       void *                stream );
+
+int
+fd_ed25519_amd_verify_txns_budget( fd_ed25519_amd_t *    eng,
+                                   ulong                 txn_cnt,
+                                   uchar const *         payload,
+                                   uint const *          txn_off,
+                                   uint const *          txn_sz,
+                                   ulong                 payload_sz,
+                                   schar *               txn_err,
+                                   uint *                sig_base,
+                                   schar *               sig_err,
+                                   ulong *               txn_tag,
+                                   ulong *               sig_tag,
+                                   ulong *               desc_off,
+                                   uchar *               desc,
+                                   ulong                 desc_cap,
+                                   fd_txn_amd_budget_t * budget );
+
+int
+fd_ed25519_amd_verify_txns_registered_budget( fd_ed25519_amd_t *    eng,
+                                              ulong                 txn_cnt,
+                                              void const * const *  txn,
+                                              ulong const *         txn_sz,
+                                              schar *               txn_err,
+                                              uint *                sig_base,
+                                              schar *               sig_err,
+                                              ulong *               txn_tag,
+                                              ulong *               sig_tag,
+                                              ulong *               desc_off,
+                                              uchar *               desc,
+                                              ulong                 desc_cap,
+                                              fd_txn_amd_budget_t * budget );
+
+int
+fd_ed25519_amd_submit_txns_budget( fd_ed25519_amd_t *    eng,
+                                   ulong                 txn_cnt,
+                                   uchar const *         payload,
+                                   uint const *          txn_off,
+                                   uint const *          txn_sz,
+                                   ulong                 payload_sz,
+                                   schar *               txn_err,
+                                   uint *                sig_base,
+                                   schar *               sig_err,
+                                   ulong *               txn_tag,
+                                   ulong *               sig_tag,
+                                   ulong *               desc_off,
+                                   uchar *               desc,
+                                   ulong                 desc_cap,
+                                   uint *                keep,
+                                   ulong *               keep_cnt,
+                                   void *                out,
+                                   ulong                 out_cap,
+                                   ulong *               emit_off,
+                                   uint *                emit_sz,
+                                   fd_txn_amd_budget_t * budget,
+                                   ulong *               ticket );
+
+int
+fd_ed25519_amd_submit_txns_registered_budget( fd_ed25519_amd_t *    eng,
+                                              ulong                 txn_cnt,
+                                              void const * const *  txn,
+                                              ulong const *         txn_sz,
+                                              schar *               txn_err,
+                                              uint *                sig_base,
+                                              schar *               sig_err,
+                                              ulong *               txn_tag,
+                                              ulong *               sig_tag,
+                                              ulong *               desc_off,
+                                              uchar *               desc,
+                                              ulong                 desc_cap,
+                                              uint *                keep,
+                                              ulong *               keep_cnt,
+                                              void *                out,
+                                              ulong                 out_cap,
+                                              ulong *               emit_off,
+                                              uint *                emit_sz,
+                                              fd_txn_amd_budget_t * budget,
+                                              ulong *               ticket );
+
 /* Signature-slot numbering of a pointer-array batch (pure host code, no
    device): the rule of fd_ed25519_amd_txn_slots, one payload per pointer.
    txn[t] is not looked at when txn_sz[t] is 0, and a NULL txn[t] reserves
