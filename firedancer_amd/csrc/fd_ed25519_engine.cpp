@@ -28,6 +28,7 @@
 
 #include "../../include/fd_ed25519_amd.h"
 #include "../../include/fd_txn_amd.h"
+#include "../../include/fd_tango_amd.h"   /* frag submissions */
 #include "fd_ed25519_kernels.h"
 #include "fd_ed25519_emit.h"   /* the layout arithmetic alone: no kernel is compiled here */
 #include "fd_txn_budget.h"     /* likewise: the record's codes, for the asserts below */
@@ -79,6 +80,7 @@ slot_free( slot_t * s ) {
   if( s->d_epack) (void)hipFree( s->d_epack );
   if( s->h_epack) (void)hipHostFree( s->h_epack );
   if( s->h_budget) (void)hipHostFree( s->h_budget );
+  if( s->d_fpack ) (void)hipFree( s->d_fpack );
   if( s->win_done ) (void)hipEventDestroy( s->win_done );
   if( s->stream ) (void)hipStreamDestroy( s->stream );
   if( s->done   ) (void)hipEventDestroy( s->done );
@@ -286,6 +288,21 @@ slot_alloc_budget( slot_t * s, ulong cap ) {
   return FD_ED25519_AMD_OK;
 }
 
+/* The slot's idle block and status plane, on its first frag submission.  The
+   block is zeroed on the slot's stream, ahead of the kernels that read it. */
+static int
+slot_alloc_frags( slot_t * s, ulong cap ) {
+  if( s->d_fpack ) return FD_ED25519_AMD_OK;
+  HIPCHK( hipMalloc( (void **)&s->d_fpack, 256UL + cap ) );
+  s->d_fstat = (int8_t *)(s->d_fpack + 256UL);
+  HIPCHK( hipMemsetAsync( s->d_fpack, 0, 256UL, s->stream ) );
+  return FD_ED25519_AMD_OK;
+}
+
+static_assert( FD_ED25519_AMD_VERDICT_FRAG_SEQ == FD_AMD_VERDICT_FRAG_SEQ && FD_ED25519_AMD_VERDICT_FRAG_BAD == FD_AMD_VERDICT_FRAG_BAD,
+               "fd_ed25519_kernels.h restates these" );
+static_assert( sizeof(fd_frag_meta_t) == 32UL && sizeof(fd_amd_gather_rec_t) == 32UL, "k_frag_list reads and writes 32-B records" );
+
 static_assert( sizeof(fd_txn_amd_budget_t) == 24UL && alignof(fd_txn_amd_budget_t) == 8UL, "fd_amd_budget_record's three words" );
 static_assert( FD_TXN_AMD_BUDGET_OK == FD_AMD_BUDGET_OK && FD_TXN_AMD_BUDGET_INVALID == FD_AMD_BUDGET_INVALID &&
                FD_TXN_AMD_BUDGET_NOPARSE == FD_AMD_BUDGET_NOPARSE && FD_TXN_AMD_BUDGET_FLAG_SET_CU == FD_AMD_BUDGET_F_CU &&
@@ -440,6 +457,12 @@ slot_launch_sig( slot_t * s, ulong n, planes_t const & p, schar * err, ulong * t
      into the mapped h_err itself */
   bool const lat = fd_amd_uses_latency_path( (uint32_t)n, 0 ) != 0;
   if( slot_verify( s, n, p, 1, NULL, lat ? s->m_err : NULL ) ) return FD_ED25519_AMD_ERR_DEVICE;
+  /* a frag submission: the items' statuses over the verdicts and 0 over their tags, ahead of everything that
+     reads either; on the latency path over the mapped verdicts too, which slot_out writes otherwise */
+  if( s->frag_arm.mcache &&
+      fd_amd_launch_frag_verdict( (uint32_t)n, s->d_fstat, s->frag_arm.mcache, s->frag_arm.depth, s->frag_arm.seq0, s->d_err,
+                                  lat ? (int8_t *)s->m_err : NULL, s->d_ws, s->stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
   if( !lat ) HIPCHK( slot_out( s, s->m_err, s->d_err, n ) );
   /* latency path: k_tag_out after the DSM kernel.  The stream is in order
      and the host waits for one event behind both outputs, so either side of
@@ -1713,6 +1736,86 @@ fd_ed25519_amd_submit_batch_registered_emit( fd_ed25519_amd_t * e, ulong n, void
   if( n > e->cap || fd_ed25519_amd_gather_layout( n, sz, e->cap, e->blob_cap, slot_gather_dst( e, s ) ) != n )
     return FD_ED25519_AMD_ERR_INVAL;
   return submit_run( e, s, keep, keep_cnt, em, ticket, [&]() -> long { return stage_batch_registered( e, s, view, n, msg, sz, sig, pub, err, tag ); } );
+}
+
+/* A frag source as the device sees it, after the submit call's checks. */
+struct frag_args_t { uint64_t mcache, chunk0; ulong depth, data_sz, frag_max, seq0; };
+
+/* What fd_ed25519_amd_submit_frags and the two _dev steps refuse about a
+   source and a count, all of it O(1): true when ( src, n ) may be launched
+   with dst = i * round_up( frag_max - 96, 16 ) below `blob`. */
+static bool
+frag_src_ok( fd_ed25519_amd_frag_src_t const * src, ulong n, ulong blob ) {
+  if( !src || !src->mcache || ( (uintptr_t)src->mcache & 31UL ) || !src->chunk0 || !src->data_sz ) return false;
+  if( !src->depth || ( src->depth & ( src->depth - 1UL ) ) || src->depth > ( 1UL << 40 ) || n > src->depth ) return false;
+  if( src->frag_max < 96UL || src->frag_max > 65535UL ) return false;
+  return n <= 0xFFFFFFFFUL && n * ( ( src->frag_max - 96UL + 15UL ) & ~15UL ) <= blob;
+}
+
+/* Stage and launch on s the n frags of a checked source: k_frag_list writes
+   the records into the slot's device d_pack and the statuses into d_fstat,
+   the unchanged k_gather runs on those records, and slot_launch_sig's tail
+   carries k_frag_verdict (frag_arm).  The host touches no line and no frag. */
+static long
+stage_frags( fd_ed25519_amd_t * e, slot_t * s, frag_args_t const & fa, ulong n, schar * err, ulong * tag ) {
+  int rc = slot_alloc_frags( s, e->cap );
+  if( rc ) return rc;
+  if( tag ) { rc = slot_alloc_tag( s, e->cap ); if( rc ) return rc; }
+  fd_amd_gather_rec_t * rec = (fd_amd_gather_rec_t *)s->d_pack;
+  if( fd_amd_launch_frag_list( (uint32_t)n, (void const *)fa.mcache, fa.depth, fa.seq0, fa.chunk0, fa.data_sz, (uint32_t)fa.frag_max,
+                               (uint64_t)(uintptr_t)s->d_fpack, rec, s->d_fstat, s->stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  /* the wave cap: slot_launch_gather's */
+  bool const lat = fd_amd_uses_latency_path( (uint32_t)n, 0 ) != 0;
+  if( fd_amd_launch_gather( (uint32_t)n, rec, s->d_pub, s->d_sig, s->d_off, s->d_sz, s->d_blob, lat ? 0u : 64u, s->stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  s->frag_arm = { (void const *)fa.mcache, fa.depth, fa.seq0 };
+  rc = slot_launch_sig( s, n, slot_planes( s ), err, tag );
+  s->frag_arm = { NULL, 0UL, 0UL };
+  return rc ? rc : (long)n;
+}
+
+extern "C" int
+fd_ed25519_amd_submit_frags( fd_ed25519_amd_t * e, fd_ed25519_amd_frag_src_t const * src, ulong seq0, ulong n, schar * err,
+                             ulong * tag, uint * keep, ulong * keep_cnt, void * out, ulong out_cap, ulong * emit_off,
+                             uint * emit_sz, ulong * ticket ) {
+  if( !e || !ticket || !n || !src || !err || KEEP_ARGS_BAD( keep, keep_cnt ) ) return FD_ED25519_AMD_ERR_INVAL;
+  emit_args_t em;
+  if( emit_args_check( &em, out, out_cap, emit_off, emit_sz, keep ) ) return FD_ED25519_AMD_ERR_INVAL;
+  if( n > e->cap || !frag_src_ok( src, n, e->blob_cap ) ) return FD_ED25519_AMD_ERR_INVAL;
+  /* every capacity by the bound, never by the data */
+  if( em.out && em.cap < n * fd_ed25519_amd_emit_bound( src->frag_max - 96UL ) ) return FD_ED25519_AMD_ERR_INVAL;
+  reg_view_t view;
+  frag_args_t fa = { 0UL, 0UL, src->depth, src->data_sz, src->frag_max, seq0 };
+  if( !view.xlat( src->mcache, 32UL*src->depth, &fa.mcache ) || !view.xlat( src->chunk0, src->data_sz, &fa.chunk0 ) )
+    return FD_ED25519_AMD_ERR_INVAL;
+  int rc;
+  slot_t * s = submit_slot( e, &rc );
+  if( !s ) return rc;
+  return submit_run( e, s, keep, keep_cnt, em, ticket, [&]() -> long { return stage_frags( e, s, fa, n, err, tag ); } );
+}
+
+extern "C" int
+fd_ed25519_amd_frag_list_dev( fd_ed25519_amd_frag_src_t const * src, ulong seq0, ulong n, void const * d_idle, void * d_rec,
+                              schar * d_status, void * stream ) {
+  if( !n ) return FD_ED25519_AMD_OK;
+  if( !frag_src_ok( src, n, 0xFFFFFFFFUL ) || !d_idle || ( (uintptr_t)d_idle & 15UL ) || !d_rec || ( (uintptr_t)d_rec & 31UL ) ||
+      !d_status )
+    return FD_ED25519_AMD_ERR_INVAL;
+  if( fd_amd_launch_frag_list( (uint32_t)n, src->mcache, src->depth, seq0, (uint64_t)(uintptr_t)src->chunk0, src->data_sz,
+                               (uint32_t)src->frag_max, (uint64_t)(uintptr_t)d_idle, (fd_amd_gather_rec_t *)d_rec,
+                               (int8_t *)d_status, (hipStream_t)stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  return FD_ED25519_AMD_OK;
+}
+
+extern "C" int
+fd_ed25519_amd_frag_check_dev( fd_ed25519_amd_frag_src_t const * src, ulong seq0, ulong n, schar * d_status, void * stream ) {
+  if( !n ) return FD_ED25519_AMD_OK;
+  if( !frag_src_ok( src, n, 0xFFFFFFFFUL ) || !d_status ) return FD_ED25519_AMD_ERR_INVAL;
+  if( fd_amd_launch_frag_check( (uint32_t)n, src->mcache, src->depth, seq0, (int8_t *)d_status, (hipStream_t)stream ) )
+    return FD_ED25519_AMD_ERR_DEVICE;
+  return FD_ED25519_AMD_OK;
 }
 
 extern "C" int

@@ -106,6 +106,16 @@ struct slot_t {
   uint8_t * h_epack; ulong * h_eoff; uint * h_esz;
   void    * m_eoff;  void  * m_esz;
   emit_args_t emit_arm;
+  /* frag submissions (fd_ed25519_amd_submit_frags; allocated by the first
+     one).  d_fpack, one device allocation: the idle block, 96 zero bytes on a
+     256-byte line, which the records of items without a frag point at, and
+     d_fstat[cap] behind it, the items' statuses (k_frag_list writes them,
+     k_frag_verdict reads them).  frag_arm: the launch under way is a frag
+     submission (mcache != NULL: its lines' device address), so the slot's
+     launch tail puts k_frag_verdict behind the verify kernels (set and
+     cleared by stage_frags). */
+  uint8_t * d_fpack; int8_t * d_fstat;
+  struct { void const * mcache; ulong depth, seq0; } frag_arm;
   /* compute budget (the _budget calls; allocated by the first call that asks
      for it): h_budget[cap], fd_txn_amd_budget_t records in mapped pinned
      memory that k_txn_budget writes in place (m_budget: its device address) */

@@ -6,9 +6,11 @@
 
    Input: one fd_amd_gather_rec_t per signature, { pub, sig, msg, sz, dst }:
    the device addresses of its 32 public-key, 64 signature and sz message
-   bytes (translated on the host from the registration table, which is the
-   only source of addresses this kernel is ever given) and the offset its
-   message gets in the chunk's blob.  Output: d_pub[32 i], d_sig[64 i],
+   bytes and the offset its message gets in the chunk's blob.  Every address
+   in a record has one of two sources: the host translated it from the
+   registration table (the pointer-array calls), or k_frag_list computed it
+   on the device (fd_ed25519_frags.h: inside the one registered data region
+   with its whole range, or the slot's own idle block).  Output: d_pub[32 i], d_sig[64 i],
    d_off[i] = dst, d_sz[i] = sz and the message at d_blob + dst -- the planes
    fd_amd_launch_verify reads, as slot_launch_dma fills them.
 

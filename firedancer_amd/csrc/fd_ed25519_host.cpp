@@ -475,6 +475,39 @@ fd_txn_amd_emit( unsigned long keep_cnt, unsigned int const * keep, void const *
   return tot;
 }
 
+/* The frag rule on the host (include/fd_tango_amd.h, "Frag submissions"):
+   steps 1 to 3 per item; single-threaded, so the recheck of step 4 reads
+   what step 1 read.  This file includes no public header (it restates the
+   reference's signatures with plain types), so the line, the source and the
+   two statuses are restated here: fd_frag_meta_t (fd_tango_base.h:146-203),
+   fd_ed25519_amd_frag_src_t, FD_ED25519_AMD_VERDICT_FRAG_SEQ / _BAD. */
+struct frag_meta_t { u64 seq, sig; u32 chunk; uint16_t sz, ctl; u32 tsorig, tspub; };
+struct frag_src_t  { frag_meta_t const * mcache; unsigned long depth; void const * chunk0; unsigned long data_sz, frag_max; };
+static_assert( sizeof(frag_meta_t) == 32 && sizeof(frag_src_t) == 40, "include/fd_tango_amd.h" );
+
+unsigned long
+fd_ed25519_amd_frags( frag_src_t const * src, unsigned long seq0, unsigned long n, signed char * status,
+                      void const ** pub, void const ** sig, void const ** msg, unsigned long * sz ) {
+  if( !src || !src->mcache || !src->chunk0 || !src->depth || ( src->depth & ( src->depth - 1UL ) ) || src->frag_max < 96UL ||
+      src->frag_max > 65535UL )
+    return 0UL;
+  unsigned long good = 0UL;
+  for( unsigned long i=0UL; i<n; i++ ) {
+    unsigned long const seq = seq0 + i;                                   /* modulo 2^64 */
+    frag_meta_t const * L = src->mcache + ( seq & ( src->depth - 1UL ) );
+    unsigned long const at = (unsigned long)L->chunk << 6, fsz = L->sz;   /* at < 2^38: the sum below cannot wrap */
+    int st = 0;
+    if( L->seq != seq ) st = -5;
+    else if( fsz < 96UL || fsz > src->frag_max || at + fsz > src->data_sz ) st = -6;
+    status[i] = (signed char)st;
+    u8 const * f = (u8 const *)src->chunk0 + at;
+    pub[i] = st ? NULL : f;  sig[i] = st ? NULL : f + 32;  msg[i] = st ? NULL : f + 96;
+    sz[i]  = st ? 0UL : fsz - 96UL;
+    good += !st;
+  }
+  return good;
+}
+
 /* The compute budget rule on the host (include/fd_txn_amd.h, "Compute
    budget"): the walk over the descriptor's instruction records, with
    fd_txn_budget.h's step, finalize and record -- the functions k_txn_budget

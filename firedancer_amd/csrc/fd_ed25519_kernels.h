@@ -222,6 +222,31 @@ typedef struct { uint64_t src; uint32_t sz, dst, tbase, pad[3]; } fd_amd_gather_
 int fd_amd_launch_gather_txn( uint32_t n, fd_amd_gather_txn_rec_t const * d_rec, uint8_t * d_blob, uint32_t * d_toff,
                               uint32_t * d_tsz, uint32_t * d_tbase, uint32_t slot_cnt, uint32_t waves, hipStream_t stream );
 
+/* Frag submissions (fd_ed25519_frags.h; include/fd_tango_amd.h, "Frag
+   submissions").  The two statuses a line can give an item, restated from
+   the public header (fd_ed25519_engine.cpp asserts the equality).
+   fd_amd_launch_frag_list: items [0, n) of the submission ( seq0, n ) over
+   d_mcache (depth lines, a power of two; device address, 32-aligned) and the
+   data region [d_chunk0, d_chunk0 + data_sz) -> d_rec[0, n), the records
+   k_gather consumes with dst = i * round_up( frag_max - 96, 16 ), and
+   d_status[0, n) (both device memory; d_rec 32-aligned).  d_idle: 96 zero
+   bytes of device memory, 16-aligned.  n * round_up( frag_max - 96, 16 )
+   < 2^32.
+   fd_amd_launch_frag_check: the recheck of every item whose status is 0.
+   fd_amd_launch_frag_verdict: the statuses over the n verdicts d_err (and
+   m_err, the mapped copy, when not NULL) and 0 over their tags in the tag
+   plane of d_ws, the workspace of a verify launch of n signatures; d_mcache
+   != NULL: the recheck first. */
+#define FD_AMD_VERDICT_FRAG_SEQ (-5)
+#define FD_AMD_VERDICT_FRAG_BAD (-6)
+int fd_amd_launch_frag_list( uint32_t n, void const * d_mcache, uint64_t depth, uint64_t seq0, uint64_t d_chunk0,
+                             uint64_t data_sz, uint32_t frag_max, uint64_t d_idle, fd_amd_gather_rec_t * d_rec,
+                             int8_t * d_status, hipStream_t stream );
+int fd_amd_launch_frag_check( uint32_t n, void const * d_mcache, uint64_t depth, uint64_t seq0, int8_t * d_status,
+                              hipStream_t stream );
+int fd_amd_launch_frag_verdict( uint32_t n, int8_t * d_status, void const * d_mcache, uint64_t depth, uint64_t seq0,
+                                int8_t * d_err, int8_t * m_err, void * d_ws, hipStream_t stream );
+
 /* n bytes device -> mapped host memory by a kernel (no DMA engine). */
 int fd_amd_launch_copy_out( void * d_dst_mapped, void const * d_src, size_t n, hipStream_t stream );
 

@@ -29,6 +29,7 @@
  *   fd_ed25519_tile.h   k_tile_persist, k_tile_synth
  *   fd_ed25519_strict.h k_strict (strict mode's overlay, after the DSM stage)
  *   fd_ed25519_gather.h k_gather, k_gather_txn (pointer-array chunks from registered memory)
+ *   fd_ed25519_frags.h  k_frag_list, k_frag_check, k_frag_verdict (a submission's frags listed from the mcache lines)
  *   fd_ed25519_keep.h   k_keep_clear, k_keep_insert, k_keep_mark, k_keep_store (a batch's survivors)
  *   fd_ed25519_window.h k_win_clear, k_win_rebuild, k_win_query, k_win_insert, k_win_head (dedup across submissions)
  * This file keeps the launch code, the batch-size policy and the small
@@ -51,6 +52,7 @@
 #include "fd_ed25519_strict.h"
 #include "../../include/fd_txn_amd.h"   /* FD_TXN_AMD_MTU: k_gather_txn's one pass */
 #include "fd_ed25519_gather.h"
+#include "fd_ed25519_frags.h"
 #include "fd_ed25519_keep.h"
 #include "fd_ed25519_window.h"
 #include "fd_ed25519_emit.h"
@@ -116,6 +118,33 @@ fd_amd_launch_gather_txn( uint32_t n, fd_amd_gather_txn_rec_t const * d_rec, uin
   u32 nb = (n + per - 1u)/per;
   if( waves && nb > waves ) nb = waves;
   hipLaunchKernelGGL( k_gather_txn, dim3(nb), dim3(64), 0, stream, n, d_rec, d_blob, d_toff, d_tsz, d_tbase, slot_cnt );
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* One lane per line / item (k_frag_list, k_frag_check, k_frag_verdict, fd_ed25519_frags.h). */
+int
+fd_amd_launch_frag_list( uint32_t n, void const * d_mcache, uint64_t depth, uint64_t seq0, uint64_t d_chunk0, uint64_t data_sz,
+                         uint32_t frag_max, uint64_t d_idle, fd_amd_gather_rec_t * d_rec, int8_t * d_status, hipStream_t stream ) {
+  if( !n ) return 0;
+  u32 const stride = ( frag_max - FRAG_HDR + 15u ) & ~15u;
+  hipLaunchKernelGGL( k_frag_list, dim3((n + 63u)/64u), dim3(64), 0, stream, n, (u8 const *)d_mcache, depth - 1UL, seq0, d_chunk0,
+                      data_sz, frag_max, stride, d_idle, d_rec, d_status );
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int
+fd_amd_launch_frag_check( uint32_t n, void const * d_mcache, uint64_t depth, uint64_t seq0, int8_t * d_status, hipStream_t stream ) {
+  if( !n ) return 0;
+  hipLaunchKernelGGL( k_frag_check, dim3((n + 63u)/64u), dim3(64), 0, stream, n, (u8 const *)d_mcache, depth - 1UL, seq0, d_status );
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int
+fd_amd_launch_frag_verdict( uint32_t n, int8_t * d_status, void const * d_mcache, uint64_t depth, uint64_t seq0, int8_t * d_err,
+                            int8_t * m_err, void * d_ws, hipStream_t stream ) {
+  if( !n ) return 0;
+  hipLaunchKernelGGL( k_frag_verdict, dim3((n + 63u)/64u), dim3(64), 0, stream, n, d_status, (u8 const *)d_mcache, depth - 1UL, seq0,
+                      d_err, m_err, (u64 *)((u8 *)d_ws + fd_amd_ws_layout( n ).tag) );
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

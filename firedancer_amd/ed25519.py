@@ -221,6 +221,11 @@ def lib():
            "fd_ed25519_amd_window_keep_dev": ([vp, ul, vp, vp, vp, vp, vp, vp], i),
            "fd_ed25519_amd_window_export": ([vp, vp], ul), "fd_ed25519_amd_window_import": ([vp, vp, ul], i),
            "fd_ed25519_amd_set_window": ([vp, vp], i), "fd_ed25519_amd_window": ([vp], vp),
+           # frag submissions: the GPU reads the frag metadata
+           "fd_ed25519_amd_frags": ([vp, ul, ul, vp, vp, vp, vp, vp], ul),
+           "fd_ed25519_amd_submit_frags": ([vp, vp, ul, ul, vp, vp, vp, vp, vp, ul, vp, vp, c_ulong_p], i),
+           "fd_ed25519_amd_frag_list_dev": ([vp, ul, ul, vp, vp, vp, vp], i),
+           "fd_ed25519_amd_frag_check_dev": ([vp, ul, ul, vp, vp], i),
            # the streaming tile's verdict mode
            "fd_verify_amd_tile_set_verdict_mode": ([vp, i], i), "fd_verify_amd_tile_verdict_mode": ([vp], i),
            # debug: k_dsmp's grid, the parked R'
@@ -432,6 +437,64 @@ def txn_emit(keep, payloads, desc_off, desc, out=None, out_cap=None):
     d = np.ascontiguousarray(desc, np.uint8)
     assert do.size == len(tb) + 1 and int(do[-1]) <= d.size
     return _emit_host(lib().fd_txn_amd_emit, keep, (_ptr(tp), _ptr(tsz), _ptr(do), _ptr(d)), len(tb), out, out_cap)
+
+
+# ---------------------------------------------------------------- frag sources
+
+VERDICT_FRAG_SEQ = -5   # FD_ED25519_AMD_VERDICT_FRAG_SEQ: the line did not (or no longer) hold the item's sequence number
+VERDICT_FRAG_BAD = -6   # FD_ED25519_AMD_VERDICT_FRAG_BAD: the line's chunk / sz name no frag of the source
+FRAG_MAX_DEFAULT = 96 + MSG_MAX
+GATHER_REC = np.dtype([("pub", "<u8"), ("sig", "<u8"), ("msg", "<u8"), ("sz", "<u4"), ("dst", "<u4")])   # fd_amd_gather_rec_t
+
+
+class FragSrc(ctypes.Structure):
+    """fd_ed25519_amd_frag_src_t (include/fd_tango_amd.h)."""
+    _fields_ = [("mcache", ctypes.c_void_p), ("depth", ctypes.c_ulong), ("chunk0", ctypes.c_void_p),
+                ("data_sz", ctypes.c_ulong), ("frag_max", ctypes.c_ulong)]
+
+
+def frag_src(mcache, region, frag_max=FRAG_MAX_DEFAULT, mcache_addr=None, chunk0_addr=None):
+    """The FragSrc of an mcache (tango.mcache_new: a FRAG_META array of depth
+    lines) and a data region (a uint8 array, chunk 0 at its first byte).
+    mcache_addr / chunk0_addr: other addresses of the same memory (the device
+    addresses the _dev calls take)."""
+    return FragSrc(int(mcache.ctypes.data if mcache_addr is None else mcache_addr), int(mcache.size),
+                   int(region.ctypes.data if chunk0_addr is None else chunk0_addr), int(region.nbytes), int(frag_max))
+
+
+def frags(mcache, region, seq0, n, frag_max=FRAG_MAX_DEFAULT):
+    """fd_ed25519_amd_frags: the frag rule on the host (no device) for items
+    (seq0, n) of the source.  Returns (good, status, pub, sig, msg, sz):
+    status int8 [n] (0, VERDICT_FRAG_SEQ or VERDICT_FRAG_BAD), the three
+    addresses as uint64 [n] and the message sizes as uint64 [n] (0 where the
+    status is nonzero), and the number of items whose status is 0.  What
+    Engine.submit_frags decides on the GPU."""
+    n = int(n)
+    src = frag_src(mcache, region, frag_max)
+    status = np.zeros(max(n, 1), np.int8)
+    pub, sig, msg, sz = (np.zeros(max(n, 1), np.uint64) for _ in range(4))
+    good = int(lib().fd_ed25519_amd_frags(ctypes.byref(src), int(seq0) & 0xFFFFFFFFFFFFFFFF, n, _ptr(status), _ptr(pub),
+                                          _ptr(sig), _ptr(msg), _ptr(sz)))
+    return good, status[:n], pub[:n], sig[:n], msg[:n], sz[:n]
+
+
+def frag_list_dev(src, seq0, n, d_idle, d_rec, d_status, stream=0):
+    """fd_ed25519_amd_frag_list_dev: k_frag_list alone, on `stream`, no sync.
+    src: a FragSrc whose mcache and chunk0 are device addresses; d_idle: 96
+    zero bytes of device memory; d_rec: n GATHER_REC records; d_status: n int8."""
+    rc = lib().fd_ed25519_amd_frag_list_dev(ctypes.byref(src), int(seq0) & 0xFFFFFFFFFFFFFFFF, int(n), d_idle, d_rec, d_status,
+                                            stream)
+    if rc:
+        raise EngineError("fd_ed25519_amd_frag_list_dev rc=%d" % rc)
+
+
+def frag_check_dev(src, seq0, n, d_status, stream=0):
+    """fd_ed25519_amd_frag_check_dev: the recheck alone (k_frag_check), on
+    `stream`, no sync: every item whose d_status is 0 and whose line no longer
+    holds seq0 + i becomes VERDICT_FRAG_SEQ."""
+    rc = lib().fd_ed25519_amd_frag_check_dev(ctypes.byref(src), int(seq0) & 0xFFFFFFFFFFFFFFFF, int(n), d_status, stream)
+    if rc:
+        raise EngineError("fd_ed25519_amd_frag_check_dev rc=%d" % rc)
 
 
 # ---------------------------------------------------------------- batch engine
@@ -656,6 +719,31 @@ class Engine:
         addr = np.array([ctypes.addressof(b) for b in bufs], np.uint64)
         return self.submit_batch_ptrs(addr[2 * n:], addr[n:2 * n], addr[:n], [len(b) for b in keep[:n]],
                                       want_tags=want_tags, registered=False, want_keep=want_keep, emit=emit)
+
+    def submit_frags(self, mcache, region, seq0, n, frag_max=FRAG_MAX_DEFAULT, want_tags=False, want_keep=False, emit=None):
+        """fd_ed25519_amd_submit_frags: items (seq0, n) of the frag source
+        (mcache, region: each inside one host_register registration) as one
+        submission; the GPU reads the lines (module function frags is the
+        rule).  Returns the ticket; the lines, the frags and the registrations
+        must stay valid until delivery.  The delivered result is what
+        submit_batch_ptrs delivers: err (VERDICT_FRAG_SEQ / VERDICT_FRAG_BAD
+        for an item without a frag), with want_tags the tags (0 for those),
+        with want_keep keep, with emit (a uint8 array of at least n *
+        emit_bound(frag_max - 96) bytes) also (emit_off, emit_sz)."""
+        n = int(n)
+        src = frag_src(mcache, region, frag_max)
+        err = np.zeros(max(n, 1), np.int8)
+        tags = np.zeros(max(n, 1), np.uint64) if want_tags else None
+        k = _Keep(n, want_keep, emit)
+        t = ctypes.c_ulong(0)
+        ea = k.args() if emit is not None else k.args() + (None, 0, None, None)
+        rc = lib().fd_ed25519_amd_submit_frags(self._h, ctypes.byref(src), int(seq0) & 0xFFFFFFFFFFFFFFFF, n, _ptr(err),
+                                               _ptr(tags) if want_tags else None, *ea, ctypes.byref(t))
+        if want_keep:
+            finish = lambda: ((err[:n], tags[:n]) if want_tags else (err[:n],)) + k.results()
+        else:
+            finish = lambda: (err[:n], tags[:n]) if want_tags else err[:n]
+        return self._submitted("fd_ed25519_amd_submit_frags", rc, t, finish, (mcache, region, emit))
 
     def submit_txns_ptrs(self, txn_ptr, txn_sz, want_sigs=False, want_tags=False, want_desc=False, registered=True,
                          want_keep=False, emit=None, want_budget=False):

@@ -52,6 +52,7 @@ def hip():
     H.hipEventElapsedTime.argtypes = [ctypes.POINTER(ctypes.c_float), vp, vp]
     H.hipHostMalloc.argtypes = [ctypes.POINTER(vp), sz, u]
     H.hipHostFree.argtypes = [vp]
+    H.hipHostGetDevicePointer.argtypes = [ctypes.POINTER(vp), vp, u]
     H.hipGetErrorString.argtypes = [i]
     H.hipGetErrorString.restype = ctypes.c_char_p
     H.hipDeviceGetName = getattr(H, "hipDeviceGetName", None)
@@ -87,6 +88,13 @@ def device_name(d=0):
     if H.hipDeviceGetName(buf, 256, int(d)) != 0:
         return "unknown"
     return buf.value.decode()
+
+
+def host_device_pointer(host_ptr):
+    """The device address of mapped or registered host memory (hipHostGetDevicePointer)."""
+    p = ctypes.c_void_p()
+    check(hip().hipHostGetDevicePointer(ctypes.byref(p), ctypes.c_void_p(int(host_ptr)), 0), "hipHostGetDevicePointer")
+    return p.value
 
 
 def synchronize():

@@ -278,7 +278,10 @@ fd_ed25519_amd_verify_soa_registered( fd_ed25519_amd_t * eng,
    a NULL array, a NULL pub[i] / sig[i], a NULL msg[i] with sz[i] > 0,
    sz[i] > blob_max, or a range the table does not hold returns
    FD_ED25519_AMD_ERR_INVAL with err (and tag) untouched and nothing in
-   flight; the GPU is never given an address the table did not produce.
+   flight; this call never gives the GPU an address the table did not
+   produce.  (fd_ed25519_amd_submit_frags, fd_tango_amd.h, widens that: there
+   every address in a record lies inside one registered data region with its
+   whole range, as computed on the device, or is the slot's own idle block.)
    Unregistering memory, or changing the pointer arrays, during the call is
    the caller's error (as for fd_ed25519_amd_verify_soa_registered).  The
    _tag form is declared with the other tagged calls below. */

@@ -540,6 +540,146 @@ fd_verify_amd_bench_stream( int           device,
                             ulong         waves,
                             double *      out );
 
+/* ===== Part 3: frag submissions: the GPU reads the frag metadata =====
+
+   fd_ed25519_amd_submit_frags is fd_ed25519_amd_submit_batch_registered_emit
+   for a caller whose items are the frags of a tango link: instead of walking
+   the mcache lines into four arrays it names the range of sequence numbers,
+   and the GPU reads the lines, checks them as a tango consumer does and lists
+   the frags for the gather itself.  The calling thread's work per submission
+   is O(1) on the way in.  With keep and emit the engine is then a verify tile
+   whose thread, per batch, waits for the last line's seq, submits, polls and
+   publishes the survivors.
+
+   The rule (one definition: the host function, the kernels and every test
+   follow it).  A frag source is
+     mcache    depth lines of fd_frag_meta_t, depth a power of two;
+     chunk0, data_sz   the data region [chunk0, chunk0 + data_sz);
+     frag_max  the largest frag accepted, 96 <= frag_max <= 65535.
+   A submission is ( seq0, n ); seq0 may be any 64-bit value and sequence
+   arithmetic is modulo 2^64, as everywhere in tango.  Item i in [0, n) is the
+   line L = mcache[ (seq0 + i) & (depth - 1) ] and gets a status:
+     1  L.seq is read.  If it is not seq0 + i the status is
+        FD_ED25519_AMD_VERDICT_FRAG_SEQ -- the line is not published yet, or
+        mid-publish (it holds the seq - 1 marker of fd_mcache_publish), or
+        was lapped.
+     2  L.chunk and L.sz are read.  The status is
+        FD_ED25519_AMD_VERDICT_FRAG_BAD if sz < 96, or sz > frag_max, or
+        ((ulong)chunk << 6) + sz > data_sz.  sig, ctl, tsorig and tspub are
+        not looked at.
+     3  Otherwise the frag at chunk0 + (chunk << 6) is
+        pub = frag[0,32) | sig = frag[32,96) | msg = frag[96,sz): the
+        PUB_SIG_MSG framing of the reference's verify tile
+        (fd_frank_verify_synth_load.c:340-347).
+     4  After the item's bytes have been copied L.seq is read again; if it is
+        not seq0 + i the status is FD_ED25519_AMD_VERDICT_FRAG_SEQ.  This is
+        the tango consumer's recheck, the only protection against a producer
+        that ignores flow control; one that honours it never triggers it.
+   An item whose status is nonzero has err[i] = the status and tag[i] = 0; it
+   is never a survivor, never enters the dedup window and gets no frame.  An
+   item whose status is 0 has the err[i] and tag[i] that
+   fd_ed25519_amd_verify_batch_registered_tag returns for ( msg, sz - 96, sig,
+   pub ) in the engine's mode at submit; keep[] is the "Survivors" / "dedup
+   window" rule over the final err[] and tag[], and the frames are the
+   "Output frames" rule of the signature family over that keep[]
+   (fd_ed25519_amd.h).
+
+   The two statuses are verdict values of their own: 0 to -3 are the
+   reference's verdicts, -4 is FD_TXN_AMD_ERR_PARSE, -10 to -12 are call
+   errors and -128 is the device marker.
+
+   Out of scope.  The transaction family: a transaction's signature-slot
+   count is data in its first payload byte and the host sizes every verify
+   launch by the slot total, so either the host reads one byte per payload --
+   the pass this call removes -- or every verify kernel takes its n from
+   device memory, a change of its own.  Also: a blocking multi-chunk form,
+   the multi-device engine, the streaming tile and its persistent kernel,
+   writing an fseq or an output mcache from the GPU, and interpreting ctl. */
+#define FD_ED25519_AMD_VERDICT_FRAG_SEQ (-5)   /* the line did not (or no longer) hold the item's sequence number */
+#define FD_ED25519_AMD_VERDICT_FRAG_BAD (-6)   /* the line's chunk / sz name no frag of the source */
+
+typedef struct {
+  fd_frag_meta_t const * mcache; ulong depth;
+  void const * chunk0; ulong data_sz;
+  ulong frag_max;
+} fd_ed25519_amd_frag_src_t;
+
+/* The rule as pure host code: no device, single-threaded, so step 4 equals
+   step 1.  Writes status[i] for i < n, and for a good item pub[i], sig[i],
+   msg[i] (the three addresses of step 3) and sz[i] = the line's sz - 96; for
+   any other item NULL, NULL, NULL and 0.  Returns the number of good items;
+   0, with nothing written, when src is NULL, its mcache or chunk0 is NULL,
+   depth is not a power of two or frag_max is outside [96, 65535].  n may
+   exceed depth (the lines repeat).  What a CPU-only caller runs and what the
+   tests check the GPU against. */
+ulong
+fd_ed25519_amd_frags( fd_ed25519_amd_frag_src_t const * src, ulong seq0, ulong n, schar * status,
+                      void const ** pub, void const ** sig, void const ** msg, ulong * sz );
+
+/* One submission over items ( seq0, n ) of src, with the most general
+   argument list: tag == NULL, keep == keep_cnt == NULL and the four emit
+   arguments NULL / 0 each behave exactly as in
+   fd_ed25519_amd_submit_batch_registered_emit.  Everything under
+   "Asynchronous submissions", "Survivors", "Output frames" and "The dedup
+   window" holds unchanged: one chunk per submission, tickets, BUSY (checked
+   after the argument checks), delivery in ticket order, outputs written only
+   by the poll or wait that reports the ticket, the mode at submit, window
+   order, FD_ED25519_AMD_ASYNC_POLL.  Frag submissions and the other
+   submissions may be mixed in flight on one engine.
+
+   FD_ED25519_AMD_ERR_INVAL, with the effect of every error return (outputs
+   and *ticket untouched, nothing more in flight): a NULL eng, src, err or
+   ticket; n == 0, n > depth, n > batch_max; depth not a power of two;
+   frag_max outside [96, 65535]; n * round_up( frag_max - 96, 16 ) >
+   blob_max; mcache[0, depth) (which must be 32-aligned) or the data region
+   not inside ONE registration of fd_ed25519_amd_host_register (only that
+   table is consulted); the keep / emit argument errors of the _emit call;
+   out_cap < n * fd_ed25519_amd_emit_bound( frag_max - 96 ).  Every capacity
+   is decided by bounds, never by the data, and all these checks are O(1) in
+   n.
+
+   The call reads no mcache line and no frag byte.  The caller keeps the
+   lines, the frags and the registrations valid until delivery, which is also
+   the point at which it may advance its in_fseq to seq0 + n.
+
+   Addresses.  The pointer-array calls give the GPU only addresses the host
+   translated through the registration table.  Here every address in a record
+   is one of two things: it lies inside the one registered data region with
+   its whole range, as computed and checked on the device in 64-bit
+   arithmetic (chunk << 6 is below 2^38, adding sz cannot wrap), or it is the
+   slot's own idle block of zero bytes.  The recheck of step 4 is made behind
+   the verify kernels, in the kernel that overrides the verdicts: later than
+   the copy, which only a producer that ignores flow control can observe. */
+int
+fd_ed25519_amd_submit_frags( fd_ed25519_amd_t * eng, fd_ed25519_amd_frag_src_t const * src, ulong seq0, ulong n,
+                             schar * err, ulong * tag, uint * keep, ulong * keep_cnt, void * out, ulong out_cap,
+                             ulong * emit_off, uint * emit_sz, ulong * ticket );
+
+/* The two steps alone, on the caller's stream, no sync; every address
+   GPU-visible: src->mcache (32-aligned) and src->chunk0 are device addresses
+   of host memory the GPU can read (the fields of src itself are read by the
+   host, now).
+   _list_dev: steps 1 to 3 for items ( seq0, n ), n <= depth, n *
+   round_up( frag_max - 96, 16 ) < 2^32.  Writes d_rec[0, n) -- 32 bytes per
+   item, 32-aligned device memory: the device addresses of pub, sig and msg as
+   three little-endian u64, then sz - 96 and dst = i * round_up( frag_max -
+   96, 16 ) as two u32; an item with a nonzero status has pub = d_idle, sig =
+   d_idle + 32 and sz 0, and msg = d_idle wherever sz is 0 -- and
+   d_status[0, n), and nothing else.  d_idle: 96 zero bytes of device memory,
+   16-aligned.
+   _check_dev: step 4 for the items whose d_status is 0; writes d_status
+   alone.
+   FD_ED25519_AMD_ERR_INVAL for a NULL or misaligned pointer, a depth that is
+   no power of two, n > depth, a frag_max outside [96, 65535] or an n beyond
+   the offset bound; n == 0 does nothing. */
+int
+fd_ed25519_amd_frag_list_dev( fd_ed25519_amd_frag_src_t const * src, ulong seq0, ulong n, void const * d_idle,
+                              void * d_rec, schar * d_status, void * stream );
+
+int
+fd_ed25519_amd_frag_check_dev( fd_ed25519_amd_frag_src_t const * src, ulong seq0, ulong n, schar * d_status,
+                               void * stream );
+
 #ifdef __cplusplus
 }
 #endif
