@@ -168,6 +168,10 @@ def ref():
         L.fd_sha512_join.restype = vp
         L.fd_ed25519_verify.argtypes = [vp, ctypes.c_ulong, vp, vp, vp]
         L.fd_ed25519_verify.restype = ctypes.c_int
+        L.fd_ed25519_public_from_private.argtypes = [vp, vp, vp]
+        L.fd_ed25519_public_from_private.restype = vp
+        L.fd_ed25519_sign.argtypes = [vp, vp, ctypes.c_ulong, vp, vp, vp]
+        L.fd_ed25519_sign.restype = vp
         L.fd_txn_parse.argtypes = [vp, ctypes.c_ulong, vp, vp]
         L.fd_txn_parse.restype = ctypes.c_ulong
         _r = L
@@ -231,17 +235,35 @@ def sc_reduce(b64):
     return out.raw
 
 
-def ref_verify(msg, sig, pub):
-    R = ref()
-    if R is None:
-        return None
+def _ref_sha(R):
+    """One fd_sha512 object for the compiled reference's calls."""
     if not hasattr(ref_verify, "_sha"):
         buf = ctypes.create_string_buffer(256 + 128)
         addr = (ctypes.addressof(buf) + 127) & ~127
         ref_verify._buf = buf
         ref_verify._sha = R.fd_sha512_join(R.fd_sha512_new(addr))
+    return ref_verify._sha
+
+
+def ref_verify(msg, sig, pub):
+    R = ref()
+    if R is None:
+        return None
     m = bytes(msg)
-    return R.fd_ed25519_verify(m if m else None, len(m), bytes(sig), bytes(pub), ref_verify._sha)
+    return R.fd_ed25519_verify(m if m else None, len(m), bytes(sig), bytes(pub), _ref_sha(R))
+
+
+def ref_sign(seed, msg):
+    """The compiled reference's own fd_ed25519_public_from_private and
+    fd_ed25519_sign: (pub, sig); None when oracle/_ref was not built."""
+    R = ref()
+    if R is None:
+        return None
+    pub, sig = ctypes.create_string_buffer(32), ctypes.create_string_buffer(64)
+    m, prv = bytes(msg), bytes(seed)
+    R.fd_ed25519_public_from_private(pub, prv, _ref_sha(R))
+    R.fd_ed25519_sign(sig, m if m else None, len(m), pub, prv, _ref_sha(R))
+    return pub.raw, sig.raw
 
 
 def stream_inputs(seed, count, szlo, szhi, mixed):

@@ -3,16 +3,21 @@
  * TEST INFRASTRUCTURE ONLY -- probe kernels around the device field / group
  * functions of the verify engine, so that tests/test_field_probe_gpu.py can
  * compare every variant limb for limb with the Python model of the
- * reference's arithmetic (tests/_fe_ref.py) on directed inputs.
+ * reference's arithmetic (tests/_fe_ref.py) on directed inputs, and around
+ * the device functions of the GPU signer (the sign_* ops), which
+ * tests/test_sign_probe_gpu.py compares with plain integer arithmetic and
+ * the RFC 8032 model of tests/_sign_ref.py.
  *
  * Only the product's stage headers that hold the probed functions are
- * included, verbatim: the field ops (fd_ed25519_dev.h) and the group ops,
- * quad and half helpers (fd_ed25519_dsm8.h, which brings in dsm4 and dsm).
- * The front, the pool, the tile kernel and the launch code are not compiled
- * here; nothing here is linked into the product library.  Every probe is
- * straight-line code (fixed trip counts only) on whole 64-lane waves: the
- * case count is padded with all-zero cases so every lane is active (the DPP
- * forms read neighbour lanes).
+ * included, verbatim: the field ops (fd_ed25519_dev.h), the group ops,
+ * quad and half helpers (fd_ed25519_dsm8.h, which brings in dsm4 and dsm)
+ * and the signer's device functions (fd_ed25519_sign.h).
+ * The front, the pool, the tile kernel, k_sign and the launch code are not
+ * compiled here; nothing here is linked into the product library.  Every
+ * probe is straight-line code (fixed trip counts only; the one exception is
+ * fe_sq_iter's fixed squaring counts inside the signer's fe_invert) on
+ * whole 64-lane waves: the case count is padded with all-zero cases so
+ * every lane is active (the DPP forms read neighbour lanes).
  *
  * Layout: arrays are case-major, [case][stride] int32.  An op's shape is
  * { lanes per case, in0 / in1 / aux / out ints per case } (fd_probe_shape).
@@ -24,6 +29,7 @@
 
 #include "../../firedancer_amd/csrc/fd_ed25519_dev.h"
 #include "../../firedancer_amd/csrc/fd_ed25519_dsm8.h"
+#include "../../firedancer_amd/csrc/fd_ed25519_sign.h"
 
 enum {
   P_MUL = 0, P_MUL_FOLD1, P_MUL_ONE, P_SQN1, P_SQN2, P_SQ_FOLD,
@@ -32,6 +38,7 @@ enum {
   P_MUL_HALF5, P_POW22523, P_FROMBYTES, P_ISNONZERO, P_ISNEGATIVE, P_SC_REDUCE,
   P_GE_DBL, P_GE_P3, P_GE_P3_FOLD, P_GE_ADD, P_GE_MADD, P_GE_TO_CACHED,
   P_QUAD_P3, P_QUAD_BODY, P_QUAD_OWNC, P_QUAD8_OWNC5, P_QUAD_CACHED_ROW,
+  P_SIGN_FE_INVERT, P_SIGN_FE_TOBYTES, P_SIGN_RECODE, P_SIGN_SCALARMULT_BASE, P_SIGN_SC_MULADD,
   P_OP_CNT
 };
 
@@ -60,6 +67,11 @@ probe_shape( int op ) {
   case P_QUAD_OWNC:                                  return { 4, 40, 40, 2, 80 };   /* C[lane], qrow[lane], {isD, neg} -> pm[lane] | C'[lane] */
   case P_QUAD8_OWNC5:                                return { 8, 40, 40, 2, 160 };  /* the same on 8 lanes: pm[lane] (joined) | C'[lane] */
   case P_QUAD_CACHED_ROW:                            return { 4, 40, 0, 0, 40 };    /* p3 -> row[lane] */
+  case P_SIGN_FE_INVERT:                             return { 1, 10, 0, 0, 10 };
+  case P_SIGN_FE_TOBYTES:                            return { 1, 10, 0, 0, 8 };     /* limbs -> 8 LE words */
+  case P_SIGN_RECODE:                                return { 1, 8, 0, 0, 16 };     /* scalar words -> 64 int8 digits, 4 per word */
+  case P_SIGN_SCALARMULT_BASE:                       return { 1, 8, 0, 0, 8 };      /* scalar words -> encoded point */
+  case P_SIGN_SC_MULADD:                             return { 1, 16, 8, 0, 8 };     /* k|a, r -> (r + k a) mod L */
   default:                                           return { 0, 0, 0, 0, 0 };
   }
 }
@@ -71,6 +83,7 @@ static char const * const probe_names[P_OP_CNT] = {
   "fe_mul_half5", "fe_pow22523", "fe_frombytes", "fe_isnonzero", "fe_isnegative", "sc_reduce",
   "ge_dbl", "ge_p1p1_to_p3", "ge_p1p1_to_p3_fold", "ge_add", "ge_madd", "ge_to_cached",
   "quad_p3", "quad_body", "quad_ownc", "quad8_ownc5", "quad_cached_row",
+  "sign_fe_invert", "sign_fe_tobytes", "sign_recode", "sign_scalarmult_base", "sign_sc_muladd",
 };
 
 __device__ __forceinline__ fe   ldfe( i32 const * p ) { fe r; _Pragma("unroll") for( int k=0; k<10; k++ ) r.v[k] = p[k]; return r; }
@@ -182,6 +195,29 @@ k_probe( i32 const * __restrict__ in0, i32 const * __restrict__ in1, i32 const *
     fe const pm = fe_join5( pm5 );
     quad8_body_ownc5( C, pm5, ldfe( b + 10*qd ), isD, neg, mD, qd, H );
     stfe( o + 10*ln, pm ); stfe( o + 80 + 10*ln, C );
+  }
+  if constexpr( OP == P_SIGN_FE_INVERT ) stfe( o, fe_invert( ldfe( a ) ) );
+  if constexpr( OP == P_SIGN_FE_TOBYTES ) {
+    u32 w[8]; fe_tobytes_w( w, ldfe( a ) );
+    _Pragma("unroll") for( int k=0; k<8; k++ ) o[k] = (i32)w[k];
+  }
+  if constexpr( OP == P_SIGN_RECODE ) {
+    u32 s[8], dig[16];
+    _Pragma("unroll") for( int k=0; k<8; k++ ) s[k] = (u32)a[k];
+    recode_radix16( dig, s );
+    _Pragma("unroll") for( int k=0; k<16; k++ ) o[k] = (i32)dig[k];
+  }
+  if constexpr( OP == P_SIGN_SCALARMULT_BASE ) {
+    u32 s[8], enc[8];
+    _Pragma("unroll") for( int k=0; k<8; k++ ) s[k] = (u32)a[k];
+    scalarmult_base_enc( enc, s );
+    _Pragma("unroll") for( int k=0; k<8; k++ ) o[k] = (i32)enc[k];
+  }
+  if constexpr( OP == P_SIGN_SC_MULADD ) {
+    u32 kk[8], aa[8], rr[8], r[8];
+    _Pragma("unroll") for( int k=0; k<8; k++ ) { kk[k] = (u32)a[k]; aa[k] = (u32)a[8+k]; rr[k] = (u32)b[k]; }
+    sc_muladd( r, kk, aa, rr );
+    _Pragma("unroll") for( int k=0; k<8; k++ ) o[k] = (i32)r[k];
   }
 }
 

@@ -1,11 +1,15 @@
 """GPU keygen + sign (fd_ed25519_amd_sign_dev, k_sign): byte-identical to
 the host signer, which test_oracle_golden pins to RFC 8032 s7.1 and to the
 reference's own signer (fd_ed25519_user.c:279-343) through the golden
-fixtures; and every GPU signature verifies."""
+fixtures; and every GPU signature verifies.  On the directed corpus of
+tests/_sign_ref.py (padding edges of both prefixed hashes, every message
+start alignment, edge seeds) the bytes are those of the independent RFC 8032
+model, and a partial batch writes its own rows only."""
 import numpy as np
 import pytest
 
 import _golden
+import _sign_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -55,3 +59,40 @@ def test_gpu_signed_batch_verifies(engine):
     pub, sig = ed25519.sign_batch_gpu(prv, blob, off, sz)
     err = engine.verify_soa(pub, sig, off, sz, blob)
     assert (err == 0).sum() >= n - 1           # an AVX limb false reject has probability ~1.6e-6
+
+
+def test_gpu_signer_matches_model_on_corpus():
+    from firedancer_amd import ed25519
+    c = _sign_ref.corpus()
+    pub, sig = ed25519.sign_batch_gpu(c.prv, c.blob, c.off, c.sz)
+    msg = _sign_ref.first_difference(c, pub, sig)
+    assert msg is None, msg
+
+
+@pytest.fixture(scope="module")
+def corpus_dev():
+    from firedancer_amd import hip
+    c = _sign_ref.corpus()
+    return c, [hip.DeviceBuffer.from_array(a) for a in (c.prv, c.off, c.sz, c.blob)]
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, None])
+def test_sign_dev_writes_rows_below_n_only(corpus_dev, n):
+    """sign_dev on the corpus's first n items (None: all of them; the count
+    is no multiple of the 64-lane block): rows below n are the model's, and
+    every byte from row n on keeps its sentinel."""
+    from firedancer_amd import ed25519, hip
+    c, d = corpus_dev
+    tot = len(c)
+    n = tot if n is None else n
+    assert n <= tot and tot % 64
+    d_pub = hip.DeviceBuffer.from_array(np.full(32 * tot, 0xe7, np.uint8))
+    d_sig = hip.DeviceBuffer.from_array(np.full(64 * tot, 0xe7, np.uint8))
+    st = hip.Stream()
+    ed25519.sign_dev(n, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d_pub.ptr, d_sig.ptr, st.handle)
+    st.synchronize()
+    pub = d_pub.to_array(np.uint8, 32 * tot).reshape(tot, 32)
+    sig = d_sig.to_array(np.uint8, 64 * tot).reshape(tot, 64)
+    msg = _sign_ref.first_difference(c, pub, sig, n)
+    assert msg is None, msg
+    assert (pub[n:] == 0xe7).all() and (sig[n:] == 0xe7).all()
